@@ -28,9 +28,18 @@ with the max-abs difference of its output from the headline's.
 reference's module graph on torch fp32 CPU (oracle/torch_cpu.py) over the same
 step.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N ...
+
+A plain run does only what the headline needs: it builds the model in the
+headline's arithmetic, warms up, times the K steps, writes the last step's
+outputs if ``--dump-outputs DIR`` is given, and prints the result line.
+Everything else described above and below -- the exchange self-check, the
+pipelined leg, the per-op HIP-event roofline, the ``f32_exact`` and
+``split16_auto`` modes, BASELINE configs 3-5 and the CPU baseline -- runs only
+with ``--full`` (where ``--no-f32``, ``--no-profile``, ``--no-configs``,
+``--no-cpu-baseline`` and ``--pipeline 1`` still switch single legs off).
 
 Rank 0 prints ONE JSON line; diagnostics go to stderr.
 """
@@ -459,6 +468,30 @@ def pipelined(a, cfg, params, spk, precision, model, x, dev):
                     "(one engine instance each); reported beside, not as, the headline"}
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(dirname: str, rank: int, world: int, tensors: dict) -> None:
+    """``--dump-outputs DIR``: what the timed path returned in its last timed
+    step, as DIR/<name>.npy (float32; rank r > 0 of a multi-GPU run writes
+    <name>_rank<r>.npy).  The inputs and weights are seeded, so two builds run
+    with the same arguments can be compared file by file.  Whole arrays at the
+    default workload (about 4 MB); if the arrays of a larger one pass 64 MB in all,
+    each is cut to a fixed seeded sample of its flattened elements (sorted
+    indices from PCG64(0)), its share of the budget in proportion to its size."""
+    os.makedirs(dirname, exist_ok=True)
+    arrs = {k: np.ascontiguousarray(v.detach().float().cpu().numpy()) for k, v in tensors.items()}
+    total = sum(v.nbytes for v in arrs.values())
+    for name, v in arrs.items():
+        if total > DUMP_MAX_BYTES:
+            keep = max(1, int(v.size * (DUMP_MAX_BYTES / total) * 0.99))
+            idx = np.sort(np.random.Generator(np.random.PCG64(0)).choice(v.size, size=keep, replace=False))
+            v = v.reshape(-1)[idx]
+        suffix = f"_rank{rank}" if world > 1 and rank > 0 else ""
+        np.save(os.path.join(dirname, f"{name}{suffix}.npy"), v)
+    log(f"bench: wrote {', '.join(sorted(arrs))} of the last timed step to {dirname}")
+
+
 def timed_region(step, steps: int, warmup: int, world: int, sync, device):
     """The contract's timed region: ``warmup`` untimed steps, then exactly
     ``steps`` steps bracketed by sync + barrier on both sides; the elapsed time
@@ -514,7 +547,7 @@ def run_mode(a, cfg, params, spk, precision, x, dev, world, rank, log_ops):
     runner = ShardedRunner(model, shard_sizes=[B] * world)   # encode -> RCCL all-gather of latents -> decode
 
     def step():
-        return runner.step(x)[1]
+        return runner.step(x)      # (latents every rank holds after the exchange, this rank's audio)
 
     from rave_amd.model import DECODE, ENCODE
     plans = ((ENCODE, T), (DECODE, Fz))
@@ -529,7 +562,10 @@ def run_mode(a, cfg, params, spk, precision, x, dev, world, rank, log_ops):
             json.dump(eff, fh, indent=0)
     tuning_info = {"source": src, "sha16": tuning_hash(eff), "entries": len(eff),
                    "retimed": (len(eff) - len(tuning)) if tuning is not None else len(eff)}
-    el, y = timed_region(step, a.steps, a.warmup, world, torch.cuda.synchronize, dev)
+    el, (z, y) = timed_region(step, a.steps, a.warmup, world, torch.cuda.synchronize, dev)
+    if a.dump_outputs and precision == a.precision:
+        dump_outputs(a.dump_outputs, rank, world, {"latents": z, "audio": y})
+    del z
     if a.timing_only_variant:     # A/B of a timing-only kernel variant: results are not meaningful
         gather_check = {"checked": False, "reason": "timing-only kernel variant"}
     else:
@@ -538,12 +574,12 @@ def run_mode(a, cfg, params, spk, precision, x, dev, world, rank, log_ops):
         model.check()     # a cooperative-unit give-up in any timed step is an error, not a number
         # the exchange checked end to end, outside the timed region: every rank's
         # rows of the gathered latents against that rank's own (raises on mismatch)
-        gather_check = runner.verify(x)
+        gather_check = runner.verify(x) if a.full else {"checked": False, "reason": "runs with --full"}
     value = world * B * T * a.steps / el
     res = {"value": round(value, 1), "ms_per_step": round(1e3 * el / a.steps, 4),
            "x_realtime": round(value / SR, 1), "dtype": DTYPE[precision], "tuning": tuning_info,
            "gather_check": gather_check}
-    if a.pipeline > 1 and world == 1 and precision == a.precision:
+    if a.full and a.pipeline > 1 and world == 1 and precision == a.precision:
         res["pipelined"] = pipelined(a, cfg, params, spk, precision, model, x, dev)
     launches = {}
     for w, _ in plans:
@@ -552,7 +588,7 @@ def run_mode(a, cfg, params, spk, precision, x, dev, world, rank, log_ops):
             if fam in FAMILIES:
                 launches[fam] = launches.get(fam, 0) + 1
     res["gemm_launches_by_family"] = launches
-    if a.no_profile:
+    if a.no_profile or not a.full:
         return res, y
 
     # ---------------------------------------------------------- roofline (HIP events per op)
@@ -689,6 +725,13 @@ def main():
                     help="no GPU: exercise the launcher / process group on gloo and print a skeleton line")
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write the last timed step's outputs (the gathered latents and "
+                         "this rank's audio) to DIR/latents.npy and DIR/audio.npy, float32")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the exchange self-check, the pipelined leg, the per-op roofline, the "
+                         "other arithmetic modes, BASELINE configs 3-5 and the CPU baseline (each with its own "
+                         "--no-* switch below); without it only the headline is timed")
     ap.add_argument("--batch", type=int, default=16, help="clips per GPU")
     ap.add_argument("--samples", type=int, default=65536, help="samples per clip")
     ap.add_argument("--config", default="v2")
@@ -723,6 +766,8 @@ def main():
     a = ap.parse_args()
     if a.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if a.timing_only_variant and not os.environ.get("RAVE_AMD_LIB_VARIANT"):
         ap.error("--timing-only-variant is for RAVE_AMD_LIB_VARIANT libraries only")
     if "WORLD_SIZE" not in os.environ:
@@ -760,13 +805,13 @@ def main():
     head, y_head = run_mode(a, cfg, params, spk, a.precision, x, dev, world, rank, rank == 0)
     exact = None
     fast = None
-    if a.precision not in ("f32", "f32_tuned") and not a.no_f32:
+    if a.full and a.precision not in ("f32", "f32_tuned") and not a.no_f32:
         # exact fp32 MFMA on every op, with the same launch-configuration autotuning as the headline
         exact, y_f32 = run_mode(a, cfg, params, spk, "f32_tuned", x, dev, world, rank, rank == 0)
         # the same input through both arithmetic modes (north star: <= 1e-4 max-abs)
         exact["headline_vs_f32_max_abs"] = float((y_head - y_f32).abs().max())
         del y_f32
-    if a.precision not in ("auto", "split16") and not a.no_f32:
+    if a.full and a.precision not in ("auto", "split16") and not a.no_f32:
         # the fastest mixed mode (per op exact fp32 or split-f16, ~22-bit operands),
         # its error against the headline on the same input
         fast, y_fast = run_mode(a, cfg, params, spk, "auto", x, dev, world, rank, rank == 0)
@@ -775,18 +820,18 @@ def main():
         del y_fast
 
     side = None
-    if world == 1 and not a.no_configs:
+    if a.full and world == 1 and not a.no_configs:
         side = side_configs(a, dev)
 
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         cpu = cpu_baseline(cfg, params, spk, B, T, a.cpu_seconds, a.cpu_threads)
 
     if rank == 0:
         out = {
             "metric": METRIC, "value": head["value"], "unit": "samples/s", "n_gpus": world,
             "ranks_seen": dist.get_world_size() if world > 1 else 1,
-            "steps": a.steps, "warmup": a.warmup, "ms_per_step": head["ms_per_step"],
+            "steps": a.steps, "warmup": a.warmup, "ms_per_step": head["ms_per_step"], "full": a.full,
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": head["dtype"],
             "precision": a.precision,

@@ -525,8 +525,22 @@ def gen_speaker(mods, out, seed=0):
         for n, v in acts.items():
             res[f"{mode}/{n}"] = v
     cc.set_padding_mode("centered")
-    np.savez_compressed(os.path.join(out, "speaker.npz"), **res)
+    save_parts(out, "speaker", res, [lambda k: k.startswith("causal/") and not k.endswith("/layer2"),
+                                     lambda k: k.endswith("/layer2")])
     return res
+
+
+def save_parts(out, name, res, parts):
+    """One fixture over several files, each below the 1 MiB limit of a committed
+    file: <name>.npz keeps the keys no predicate of ``parts`` takes, and
+    <name>.part<i>.npz the keys of predicate i (first match).  The ``golden``
+    fixture of tests/conftest.py merges them back into one dict."""
+    files = [{} for _ in range(len(parts) + 1)]
+    for k, v in res.items():
+        i = next((i + 1 for i, p in enumerate(parts) if p(k)), 0)
+        files[i][k] = v
+    for i, f in enumerate(files):
+        np.savez_compressed(os.path.join(out, f"{name}.npz" if i == 0 else f"{name}.part{i}.npz"), **f)
 
 
 def gen_resampler(mods, out):

@@ -3,7 +3,7 @@
 # arithmetic modes the bench line reports -- the headline (f32_bf3: fp32 on every
 # op, exact-fp32 MFMA or bf16x3), f32_tuned (exact fp32 MFMA on every op) and the
 # mixed line (auto: split-f16 / fp32 per op):
-#   1. the plain bench line (with the CPU baseline), then each mode alone,
+#   1. the full bench line (bench.py --full, with the CPU baseline), then each mode alone,
 #   2. rocprofv3 --kernel-trace --stats of the same command (per-kernel times),
 #   3./4. separate --pmc FETCH_SIZE / --pmc WRITE_SIZE passes (HBM traffic; the two
 #      counters do not fit one gfx950 pass),
@@ -21,8 +21,8 @@ ONLY=${2:-all}      # all | bf3 (the f32_bf3 headline's passes only)
 OUT=$R/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-QUIET="--no-cpu-baseline --pipeline 1 --no-configs"
-timeout -k 10 300 python3 $R/bench.py --steps 10 --warmup 3 > "$OUT/bench.json" 2> "$OUT/bench.err"
+QUIET="--full --no-cpu-baseline --pipeline 1 --no-configs"
+timeout -k 10 300 python3 $R/bench.py --full --steps 10 --warmup 3 > "$OUT/bench.json" 2> "$OUT/bench.err"
 echo "bench: $(head -c 400 $OUT/bench.json)"
 gemm_rows() {   # counter CSVs are large; keep the GEMM-family rows only
     head -n 1 "$1" > "$1.gemm"
