@@ -619,11 +619,15 @@ static int resolve(const rave_conv1d_args& a, const ConvKArgs& k, int taps, Laun
     ConfigCode cc;
     const bool dec = decode_config(a.config, cc);
     if (dec && (cc.tile == kRowsTile || cc.tile == kRowsTile8)) {   // row-sliced skinny-N (one launch, no K split)
+        const int rt = cc.tile == kRowsTile8 ? 8 : cc.sep ? 32 : 16;
+        // (every refusal of conv1d_gemv_rows is made here, so that the workspace
+        // query and the launch answer alike)
         RAVE_CHECK_ARG(cc.S == 1 && k.U <= kRowsMaxN && (cc.tile == kRowsTile || !cc.sep) &&
-                           gemv_rows_fits(taps, k.U, k.d, k.transposed != 0, k.nchunks, rows_nmax(k.U)),
+                           gemv_rows_fits(taps, k.U, k.d, k.transposed != 0, k.nchunks, rows_nmax(k.U)) &&
+                           rows_tile_ok(k, rt),
                        "conv1d: gemv rows config not valid for these args (see rave_conv1d_configs)");
         c = {0, rows_nmax(k.U), 1};
-        c.rows = cc.tile == kRowsTile8 ? 8 : cc.sep ? 32 : 16;
+        c.rows = rt;
         return RAVE_OK;
     }
     if (dec && is_gemv_tile(cc.tile)) {   // the skinny-N family (conv_gemv.hip)
@@ -695,7 +699,7 @@ extern "C" int rave_conv1d_configs(const rave_conv1d_args* p, int32_t* cfgs, int
     if (k.U <= kRowsMaxN && gemv_rows_fits(taps, k.U, k.d, k.transposed != 0, k.nchunks, rows_nmax(k.U)))
         for (int v = 0; v < 3; ++v) {
             const int rt = v == 0 ? 8 : v == 1 ? 16 : 32;
-            if (k.transposed && k.split_row < k.M && k.split_row % rt != 0) continue;
+            if (!rows_tile_ok(k, rt)) continue;
             if (n < max_cfgs && cfgs) cfgs[n] = v == 0 ? encode_config(kRowsTile8, 1, 0) : encode_config(kRowsTile, 1, v - 1);
             ++n;
         }

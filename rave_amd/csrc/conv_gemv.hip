@@ -460,7 +460,7 @@ int conv1d_gemv_rows(ConvKArgs k, int taps, int nmax, int rt, hipStream_t st) {
     const int stv = taps == 4 ? 2 : taps == 8 ? 4 : 1;
     k.XW = gemv_xw(taps, stv, k.U, k.d, k.transposed != 0);
     if (!gemv_rows_fits(taps, k.U, k.d, k.transposed != 0, k.nchunks, nmax) || (rt != 8 && rt != 16 && rt != 32) ||
-        (k.transposed && k.split_row < k.M && k.split_row % rt != 0)) {
+        !rows_tile_ok(k, rt)) {
         set_error("conv1d(gemv rows): window exceeds the staging area, or too many columns");
         return RAVE_ERR_UNSUPPORTED;
     }

@@ -137,6 +137,10 @@ constexpr int kRowsTile = 14, kRowsTile8 = 15, kRowsMaxN = 32;
 bool gemv_rows_fits(int taps, int U, int d, bool transposed, int nchunks, int nmax);
 int conv1d_gemv_rows(ConvKArgs k, int taps, int nmax, int rt, hipStream_t st);
 inline int rows_nmax(int U) { int n = 4; while (n < U) n *= 2; return n; }
+// a row tile of rt rows may not straddle the ConvT phase-group boundary
+inline bool rows_tile_ok(const ConvKArgs& k, int rt) {
+    return !(k.transposed && k.split_row < k.M && k.split_row % rt != 0);
+}
 
 // rave_conv1d_args.config: 0 = heuristic, else 1 + tile + 16 (S - 1) + 512 sep
 // (tile: index into the precision's tile table; S: K-splits; sep: split-K

@@ -1085,19 +1085,15 @@ CACHED_UNIT_CASES = [
 ]
 
 
-@pytest.mark.parametrize("precision", ["f32", "split16", "f32_ring", "bf16x3"])
-@pytest.mark.parametrize("case", CACHED_UNIT_CASES, ids=[str(c) for c in CACHED_UNIT_CASES])
-def test_residual_unit_cached_form(N, dev, case, precision):
-    """The cached (streaming) fused unit: x holds need = 2d history columns then
-    the block (x_len = 2d + T, pad_left 0, rows wider than x_len), the residual
-    is x shifted by res_shift = 2d - delay (AlignBranches: causal delay 0,
-    centred d; rave/blocks.py:32-46, cached_conv convs pad nothing), against
-    the oracle on the same window."""
+def run_cached_unit(N, dev, case, prec, y_pad=0, calls=1):
+    """One cached-form fused unit launch on seeded operands: x holds need = 2d
+    history columns then the block (x_len = 2d + T, pad_left 0, 16-byte rows wider
+    than x_len whose padding is NaN), the residual is x shifted by res_shift.
+    Returns (y with its y_pad extra NaN-prefilled columns per row, the float64
+    oracle on the same window, the cooperative workspace or None); with calls > 1
+    every further call must reproduce the first bitwise."""
     from oracle.rave_oracle import conv1d, leaky_relu, snake
     C, d, act, causal, B, T, coop = case
-    prec = N.PRECISION[precision]
-    if not N.unit_supported(C, prec):
-        pytest.skip(f"no fused {precision} unit for C={C}")
     need = 2 * d
     rs = need - (0 if causal else d)
     XL = need + T
@@ -1117,12 +1113,13 @@ def test_residual_unit_cached_form(N, dev, case, precision):
     packed = torch.from_numpy(N.pack_unit_weight(w1, w2, C, precision=prec)).to(dev)
     xd = torch.from_numpy(xw).to(dev)
     dd = {k: torch.from_numpy(v).to(dev) for k, v in dict(b1=b1, b2=b2, a0=a0, a2=a2).items()}
-    y = torch.full((B, C, T), float("nan"), device=dev)
+    YS = T + y_pad
+    y = torch.full((B, C, YS), float("nan"), device=dev)
 
     def args(ws):
         return N.UnitArgs(channels=C, batch=B, t_len=T, dilation=d, pad_left=0, act=N.ACT[act],
                           leaky_slope=0.2, precision=prec, x=xd.data_ptr(), x_sb=C * SC, x_sc=SC, y=y.data_ptr(),
-                          y_sb=C * T, y_sc=T, weight=packed.data_ptr(), bias1=dd["b1"].data_ptr(),
+                          y_sb=C * YS, y_sc=YS, weight=packed.data_ptr(), bias1=dd["b1"].data_ptr(),
                           bias2=dd["b2"].data_ptr(), alpha0=dd["a0"].data_ptr() if act == "snake" else None,
                           alpha2=dd["a2"].data_ptr() if act == "snake" else None,
                           workspace=ws.data_ptr() if ws is not None else None, x_len=XL, res_shift=rs,
@@ -1132,9 +1129,29 @@ def test_residual_unit_cached_form(N, dev, case, precision):
         nws = N.lib.rave_unit_workspace(C_.byref(args(None)))
         if nws > 0:
             ws = torch.zeros(nws, device=dev)
-    N.check(N.lib.rave_residual_unit(C_.byref(args(ws)), C_.c_void_p(torch.cuda.current_stream().cuda_stream)))
-    torch.cuda.synchronize()
-    got = y.cpu().numpy()
+    got = None
+    for _ in range(calls):
+        y.fill_(float("nan"))
+        N.check(N.lib.rave_residual_unit(C_.byref(args(ws)), C_.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        torch.cuda.synchronize()
+        out = y.cpu().numpy()
+        assert got is None or np.array_equal(out, got, equal_nan=True)
+        got = out
+    return got, ref, ws
+
+
+@pytest.mark.parametrize("precision", ["f32", "split16", "f32_ring", "bf16x3"])
+@pytest.mark.parametrize("case", CACHED_UNIT_CASES, ids=[str(c) for c in CACHED_UNIT_CASES])
+def test_residual_unit_cached_form(N, dev, case, precision):
+    """The cached (streaming) fused unit: x holds need = 2d history columns then
+    the block (x_len = 2d + T, pad_left 0, rows wider than x_len), the residual
+    is x shifted by res_shift = 2d - delay (AlignBranches: causal delay 0,
+    centred d; rave/blocks.py:32-46, cached_conv convs pad nothing), against
+    the oracle on the same window."""
+    prec = N.PRECISION[precision]
+    if not N.unit_supported(case[0], prec):
+        pytest.skip(f"no fused {precision} unit for C={case[0]}")
+    got, ref, ws = run_cached_unit(N, dev, case, prec)
     assert np.isfinite(got).all()
     assert maxabs(got, ref) <= 2e-5 * max(1.0, float(np.abs(ref).max()))
     if ws is not None:
