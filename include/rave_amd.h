@@ -33,6 +33,9 @@
  *                        rave_pqmf_synthesis in one launch (split-f16).
  *   rave_stft_mag /      core.MultiScaleSTFT and core.AudioDistanceV1 rave/core.py:278-353
  *   rave_audio_distance  (the metric of RAVE.validation_step rave/model.py:636-686).
+ *   rave_yin             pitch_utils.estimate / get_pitch rave/pitch_utils.py:15-96.
+ *   rave_f0_onehot /     pitch_utils.get_f0_norm ('abs') + one_hot rave/pitch_utils.py:98-127,
+ *   rave_pitch_onehot    the f0 channels of ScriptedRAVE.myforward scripts/export.py:358-397.
  *   rave_plan_*          RAVE.encode / decode / forward rave/model.py:594-634 as
  *                        one pre-built launch sequence (the module graph).
  */
@@ -46,7 +49,7 @@
 extern "C" {
 #endif
 
-#define RAVE_ABI_VERSION 19
+#define RAVE_ABI_VERSION 20
 /* int32 arrival counters at the head of every split-K workspace (rave_conv1d_args.partial) */
 #define RAVE_SPLITK_TICKETS 4096
 /* The last of those words is reserved: no conv ticket uses it.  A cooperative
@@ -692,6 +695,76 @@ typedef struct rave_distance_args {
 } rave_distance_args;
 int64_t rave_audio_distance_workspace(const rave_distance_args* a);
 int rave_audio_distance(const rave_distance_args* a, void* stream);
+
+/* ================================================================ pitch conditioning
+ * The YIN estimator of rave/pitch_utils.py (estimate, _frame, _diff, _search
+ * :15-86, bound by get_pitch :90-96) and the quantiser that turns an f0 contour
+ * into the (bins + 1)-channel one-hot ScriptedRAVE.myforward concatenates after
+ * the latent and the speaker embedding (one_hot / quantize_f0_norm / get_f0_norm
+ * in the default 'abs' mode :98-127, scripts/export.py:358-397), csrc/pitch.hip.
+ *
+ * rave_yin: audio (rows, t_len) -> f0 (rows, frames) fp32, estimate()'s
+ * semantics, quirks included.  Host side, in the reference's order:
+ *   tau_min = (int)(sample_rate / pitch_max), tau_max = (int)(sample_rate / pitch_min),
+ *   L = 2 tau_max, stride = (int)(frame_stride * sample_rate)   (frame_stride in seconds)
+ *   frames = t_len < L ? 1 : (t_len - L) / stride + 1   (unfold; a signal shorter
+ *   than L is zero-padded on the right to one frame).
+ * Per frame, with sq[i] = sum_{j<i} x_j^2:
+ *   d(tau)  = sq[L] + (sq[L - tau] - sq[tau]) - 2 sum_{j=0}^{L-1-tau} x_j x_{j+tau},  tau < tau_max
+ *   cmdf[i] = d(i+1) (i+1) / max(sum_{k<=i} d(k+1), 1e-5),  then the slice [tau_min:]
+ *   first = first index with cmdf < threshold; index 0 or none: unvoiced (f0 = 0)
+ *   idx   = first index >= first where cmdf[j+1] - cmdf[j] >= 0 (the last index counts as rising)
+ *   f0    = sample_rate / (idx + tau_min + 1)   (an fp32 division)
+ * The autocorrelation is the direct sum, not the reference's FFT; it, the prefix
+ * sums, the cmdf and the search's comparisons are carried in double (fp32
+ * products are exact there), so the decisions are those of the reference run in
+ * float64.  `cmdf`, when not null, receives the sliced cmdf rounded to fp32,
+ * (rows, frames, tau_max - 1 - tau_min).  L <= 4410 (estimate()'s own 20 Hz
+ * default at 44.1 kHz); a longer frame is RAVE_ERR_UNSUPPORTED.  RAVE_ERR_ARG:
+ * pitch_max <= pitch_min, tau_min >= tau_max - 1 (nothing to search), a stride
+ * below one sample, null pointers, x_sr != t_len (rows must be contiguous).
+ * rave_yin_shape writes {tau_min, tau_max, L, stride, frames} (pointers ignored).
+ *
+ * rave_f0_onehot: f0 (batch, frames) -> y[b, c, t], c <= bins, written through
+ * y_sb / y_sc (time stride 1) so that the one-hot can land in the tail channels
+ * of a decoder-input tensor.  v = (log f0 - log_lo) / log_span + 0.5 in fp32;
+ * the class is bucketize(v, linspace(0, 1, bins + 1), right=True) - 1, and class
+ * `bins` is the catch-all: f0 = 0 (log of NaN), v < 0 (index -1 wraps) and
+ * v >= 1.  The op writes all (bins + 1) frames values per batch item, zeros
+ * included.  log_lo = log 40 and log_span = log(400 - log 40) (the reference's
+ * arithmetic as written) come from the host, computed in float64 and rounded
+ * once.  bins: a power of two <= 4096, where the edges are exact
+ * (RAVE_ERR_UNSUPPORTED otherwise).
+ *
+ * rave_pitch_onehot: audio -> the strided one-hot in one launch (a->f0 and
+ * a->cmdf optional, h->f0 ignored; h->batch == a->rows, h->frames == frames);
+ * bitwise the composition of the two ops above.
+ *
+ * All three validate before any launch, allocate nothing, use no atomics (reruns
+ * are bitwise identical), and are plain asynchronous launches on the stream. */
+typedef struct rave_yin_args {
+    int32_t rows, t_len, sample_rate, _pad0;
+    double pitch_min, pitch_max;  /* Hz */
+    double frame_stride;          /* seconds */
+    double threshold;             /* 0.1 */
+    int64_t x_sr;                 /* row stride of x in floats: must equal t_len */
+    const float* x;               /* (rows, t_len) */
+    float* f0;                    /* (rows, frames) */
+    float* cmdf;                  /* optional (rows, frames, tau_max - 1 - tau_min) */
+} rave_yin_args;
+int rave_yin_shape(const rave_yin_args* a, int32_t* out5);
+int rave_yin(const rave_yin_args* a, void* stream);
+
+typedef struct rave_f0_onehot_args {
+    int32_t batch, frames, bins;  /* bins + 1 channels */
+    int32_t _pad0;
+    float log_lo, log_span;
+    int64_t y_sb, y_sc;           /* in floats */
+    const float* f0;              /* (batch, frames) contiguous */
+    float* y;
+} rave_f0_onehot_args;
+int rave_f0_onehot(const rave_f0_onehot_args* a, void* stream);
+int rave_pitch_onehot(const rave_yin_args* a, const rave_f0_onehot_args* h, void* stream);
 
 /* ================================================================ model engine
  * The whole RAVE.encode / decode / forward (rave/model.py:594-634) behind one

@@ -7,7 +7,8 @@ config / graph / weight utilities are importable without it.
 """
 from .config import RaveConfig, get_config  # noqa: F401
 
-__all__ = ["RaveConfig", "get_config", "RAVE", "AudioDistance", "MultiScaleSTFT"]
+__all__ = ["RaveConfig", "get_config", "RAVE", "AudioDistance", "MultiScaleSTFT",
+           "Yin", "F0OneHot", "PitchConditioner"]
 
 
 def __getattr__(name):
@@ -20,4 +21,7 @@ def __getattr__(name):
     if name in ("AudioDistance", "MultiScaleSTFT"):
         from . import distance
         return getattr(distance, name)
+    if name in ("Yin", "F0OneHot", "PitchConditioner"):
+        from . import pitch
+        return getattr(pitch, name)
     raise AttributeError(name)

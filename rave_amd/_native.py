@@ -42,7 +42,7 @@ OP_UNIT = 11
 OP_STACK = 12
 OP_HEAD = 13
 OP_TAIL = 14
-ABI_VERSION = 19
+ABI_VERSION = 20
 SPLITK_TICKETS = 4096       # RAVE_SPLITK_TICKETS: zeroed int32 counters at the head of a split-K workspace
 SPLITK_STATUS_WORD = SPLITK_TICKETS - 1   # RAVE_SPLITK_STATUS_WORD: the cooperative unit's give-up word
 
@@ -210,6 +210,19 @@ class DistanceArgs(C.Structure):
                 ("workspace", vp), ("out", vp)]
 
 
+class YinArgs(C.Structure):
+    _fields_ = [("rows", i32), ("t_len", i32), ("sample_rate", i32), ("_pad0", i32),
+                ("pitch_min", C.c_double), ("pitch_max", C.c_double),
+                ("frame_stride", C.c_double), ("threshold", C.c_double),
+                ("x_sr", i64), ("x", vp), ("f0", vp), ("cmdf", vp)]
+
+
+class F0OneHotArgs(C.Structure):
+    _fields_ = [("batch", i32), ("frames", i32), ("bins", i32), ("_pad0", i32),
+                ("log_lo", f32), ("log_span", f32),
+                ("y_sb", i64), ("y_sc", i64), ("f0", vp), ("y", vp)]
+
+
 MAX_RATIOS = 8
 MAX_DILATIONS = 8
 
@@ -250,7 +263,7 @@ class Reloc(C.Structure):
 STRUCTS = [ConvArgs, AnalysisArgs, SynthesisArgs, FillArgs, RvqArgs, ShiftArgs, PlanOp, Reloc,
            CopyArgs, NoiseArgs, AdainArgs, UnitArgs, StackArgs, ModelConfig, Param, OpInfo,
            FirArgs, RowStatsArgs, AttnPoolArgs, LinearArgs, MaxPoolArgs, EdgeArgs,
-           StftArgs, DistanceArgs]
+           StftArgs, DistanceArgs, YinArgs, F0OneHotArgs]
 
 # every exported symbol of include/rave_amd.h
 EXPORTS = [
@@ -282,6 +295,7 @@ EXPORTS = [
     "rave_encoder_head_pack_filter_f32", "rave_decoder_tail_pack_filter_f32",
     "rave_stft_table_size", "rave_stft_pack_table", "rave_stft_mag",
     "rave_audio_distance_workspace", "rave_audio_distance",
+    "rave_yin_shape", "rave_yin", "rave_f0_onehot", "rave_pitch_onehot",
 ]
 EDGE_FILTER_FLOATS = 8836   # RAVE_EDGE_FILTER_FLOATS
 
@@ -350,6 +364,10 @@ def _load():
     lib.rave_audio_distance_workspace.argtypes = [C.POINTER(DistanceArgs)]
     lib.rave_audio_distance_workspace.restype = i64
     lib.rave_audio_distance.argtypes = [C.POINTER(DistanceArgs), vp]
+    lib.rave_yin_shape.argtypes = [C.POINTER(YinArgs), C.POINTER(i32)]
+    lib.rave_yin.argtypes = [C.POINTER(YinArgs), vp]
+    lib.rave_f0_onehot.argtypes = [C.POINTER(F0OneHotArgs), vp]
+    lib.rave_pitch_onehot.argtypes = [C.POINTER(YinArgs), C.POINTER(F0OneHotArgs), vp]
     lib.rave_plan_create.argtypes = [C.POINTER(PlanOp), C.c_int, C.POINTER(Reloc), C.c_int,
                                      C.POINTER(vp)]
     lib.rave_plan_run.argtypes = [vp, C.POINTER(vp), C.c_int, vp]
