@@ -563,7 +563,12 @@ int rave_plan_op_times(rave_plan* plan, float* ms, int n);
 /* y[i] = lo + (hi - lo) * u_i, u_i in [0, 1) from a counter-based hash of
  * (seed, i): the device draw behind torch.rand_like of NoiseGeneratorV2
  * (rave/blocks.py:287) when the caller supplies no noise, and the scratch
- * inputs of the engine's launch-configuration timing. */
+ * inputs of the engine's launch-configuration timing.  With mix() the
+ * splitmix64 finaliser and G = 0x9E3779B97F4A7C15: key = mix(seed + G) on the
+ * host, u_i = (mix(key + G (i + 1)) >> 40) / 2^24.  The seed is hashed before
+ * it meets the counter, so any two seeds (consecutive ones, or ones G apart)
+ * give unrelated sequences; one seed always gives the same values, whatever
+ * the launch geometry. */
 int rave_fill_uniform(float* y, int64_t n, uint64_t seed, float lo, float hi, void* stream);
 
 /* ================================================================ edges of the path

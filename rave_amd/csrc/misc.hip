@@ -301,15 +301,26 @@ __global__ void rvq_decode_kernel(rave_rvq_args a) {
     }
 }
 
-// Counter-based uniform draw: a splitmix64 finaliser of (seed, index), top 24
-// bits -> [0, 1).  Stateless, so any launch geometry gives the same values.
-__global__ __launch_bounds__(256) void fill_uniform_kernel(float* y, int64_t n, uint64_t seed, float lo,
+// Counter-based uniform draw.  mix64 is splitmix64's finaliser, kGolden its
+// increment.  The host hashes the caller's seed into the call's stream key,
+// key = mix64(seed + kGolden) (splitmix64's first output for that seed);
+// element i is mix64(key + kGolden * (i + 1)), the outputs of splitmix64 seeded
+// with key, top 24 bits -> [0, 1).  Stateless, so any launch geometry gives the
+// same values.  The seed must be hashed: fed to the counter as it is, seeds
+// that differ by a multiple of kGolden (the engine's base + kGolden * call)
+// would give the same sequence moved by that many elements.
+constexpr uint64_t kGolden = 0x9E3779B97F4A7C15ull;
+
+__host__ __device__ inline uint64_t mix64(uint64_t z) {
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+__global__ __launch_bounds__(256) void fill_uniform_kernel(float* y, int64_t n, uint64_t key, float lo,
                                                            float scale) {
     for (int64_t i = blockIdx.x * 256ll + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
-        uint64_t z = seed + 0x9E3779B97F4A7C15ull * (uint64_t)(i + 1);
-        z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-        z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-        z ^= z >> 31;
+        const uint64_t z = mix64(key + kGolden * (uint64_t)(i + 1));
         y[i] = lo + scale * ((float)(uint32_t)(z >> 40) * (1.0f / 16777216.0f));
     }
 }
@@ -322,7 +333,8 @@ extern "C" int rave_fill_uniform(float* y, int64_t n, uint64_t seed, float lo, f
     RAVE_CHECK_ARG(y && n >= 0, "fill_uniform: bad arguments");
     if (n == 0) return RAVE_OK;
     const int blocks = (int)std::min<int64_t>(ceil_div64(n, 256), 2048);
-    launch(fill_uniform_kernel, dim3(blocks), dim3(256), 0, as_stream(stream), y, n, seed, lo, hi - lo);
+    launch(fill_uniform_kernel, dim3(blocks), dim3(256), 0, as_stream(stream), y, n,
+           mix64(seed + kGolden), lo, hi - lo);
     return launch_status("fill_uniform_kernel");
 }
 
