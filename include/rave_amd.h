@@ -49,7 +49,7 @@
 extern "C" {
 #endif
 
-#define RAVE_ABI_VERSION 20
+#define RAVE_ABI_VERSION 21
 /* int32 arrival counters at the head of every split-K workspace (rave_conv1d_args.partial) */
 #define RAVE_SPLITK_TICKETS 4096
 /* The last of those words is reserved: no conv ticket uses it.  A cooperative
@@ -237,9 +237,12 @@ typedef struct rave_pqmf_synthesis_args {
 int rave_pqmf_synthesis(const rave_pqmf_synthesis_args* a, void* stream);
 
 /* ---------------------------------------------------------------- misc */
-/* y[b, c, t] = values[c] for c < channels, t < t_len (speaker concat) */
+/* y[b, c, t] = values[b * values_sb + c] for c < channels, t < t_len (speaker
+ * concat).  values_sb: row stride of `values` in floats; 0 (a zero-initialised
+ * struct) broadcasts one vector of `channels` floats to every batch row, any
+ * other value reads row b of a (batch, values_sb) table. */
 typedef struct rave_fill_args {
-    int32_t batch, channels, t_len, _pad0;
+    int32_t batch, channels, t_len, values_sb;
     float* y; int64_t y_sb, y_sc;
     const float* values;
 } rave_fill_args;
@@ -438,8 +441,9 @@ int rave_residual_stack(const rave_stack_args* a, void* stream);
  *   x: audio (B, 1, 16 * frames), x_sb; y: (B, conv_c_out, frames).
  *   filter: rave_encoder_head_pack_filter image; conv_c_in <= 8 bands, conv_c_out <= 64,
  *   conv_kernel 7.
- *   fill_channels > 0: also fill_y[b, c, t] = fill_values[c], t < fill_t (the
- *   speaker concat of RAVE.encode, rave/model.py:618-620).
+ *   fill_channels > 0: also fill_y[b, c, t] = fill_values[b * fill_vs + c],
+ *   t < fill_t (the speaker concat of RAVE.encode, rave/model.py:618-620;
+ *   fill_vs 0: one vector for every row, as rave_fill_args.values_sb).
  * rave_decoder_tail: GeneratorV2's act + conv (rave/blocks.py:691-696), its
  * epilogue (:699-707) and CachedPQMF.inverse (rave/pqmf.py:275-284):
  *   w = bias + conv_k(act(x))          conv_c_in 64 -> conv_c_out 32 (mode 1) / 16 (mode 2)
@@ -474,6 +478,7 @@ typedef struct rave_edge_args {
     const float* noise; int64_t n_sb, n_sc;   /* tail: (B, 16, frames) or NULL             */
     float* fill_y;      int64_t f_sb, f_sc;
     const float* fill_values;
+    int64_t fill_vs;    /* row stride of fill_values in floats; 0: one shared vector       */
 } rave_edge_args;
 int rave_encoder_head(const rave_edge_args* a, void* stream);
 int rave_decoder_tail(const rave_edge_args* a, void* stream);
@@ -823,6 +828,7 @@ typedef struct rave_model_config {
     int32_t rvq_quantizers;       /* 0 = no RVQ; 16 (discrete.gin)                           */
     int32_t rvq_codebook_size;    /* 1024                                                    */
     int32_t fuse_units;           /* 1: fused Residual(DilatedUnit) / residual-stack kernels */
+    int32_t speaker_rows;         /* rows of the per-row speaker table; 0 = 64 (cc.MAX_BATCH_SIZE) */
 } rave_model_config;
 
 /* One named parameter in the reference's state_dict naming
@@ -886,11 +892,36 @@ int rave_model_noise_shape(const rave_model* m, int batch, int frames, int64_t* 
  * existing streams pick a new row0 up at their next block. */
 int rave_model_adain_control(rave_model* m, int learn_x, int learn_y, int reset_x, int reset_y, void* stream);
 int rave_model_set_row0(rave_model* m, int row0);
-/* Replace the constant speaker embedding the encode / decode_codes paths
- * concatenate (speaker_size floats, host or device memory) -- the nn~
- * `speaker` attribute's choice among embeddings (scripts/export.py:384-396).
- * Asynchronous on `stream`; later calls on that stream see the new value. */
+/* Speaker conditioning.  The encode / decode_codes paths concatenate a speaker
+ * embedding behind every latent frame.  A model holds one shared vector and a
+ * table of speaker_rows x speaker_size floats, and is in one of two modes:
+ *   shared (the state after create): every batch row of every call reads the
+ *     one vector -- the nn~ `speaker` attribute's choice among embeddings
+ *     (scripts/export.py:384-396).  rave_model_set_speaker replaces it
+ *     (speaker_size floats) and selects this mode.
+ *   per-row: batch row b of every call reads table row speaker_row0 + b, the
+ *     per-clip embedding of the reference's training / validation steps
+ *     (rave/model.py:669-675, 714-729).  rave_model_set_speakers writes table
+ *     rows [row0, row0 + rows) from `emb` (rows x speaker_size floats, row-major)
+ *     and selects this mode; rows outside the written range keep their values
+ *     (zero after create).  rave_model_set_speaker_row0 sets speaker_row0 (a
+ *     data-parallel shard's first row of a table filled once; 0 after create).
+ *     A call, a stream block or a table write whose rows would pass the table's
+ *     end returns RAVE_ERR_ARG before anything is launched or copied.
+ * `speaker` / `emb` may be host or device memory.  The copy is asynchronous and
+ * ORDERED ON `stream`: only work queued on that stream afterwards (or on a
+ * stream that waits on it) is sure to see the new values.  That includes the
+ * blocks of existing rave_stream objects, which pick a new value, mode or row0
+ * up at their next block: a graph-mode stream refills its staged speaker
+ * channels once per change, on the stream its block is given, so a block run on
+ * another stream without such a wait may keep the old speaker until the next
+ * change.  Streams hold no speaker state of their own (there is no
+ * rave_stream_set_speaker*): these calls are the stream interface too. */
 int rave_model_set_speaker(rave_model* m, const float* speaker, void* stream);
+int rave_model_set_speakers(rave_model* m, const float* emb, int rows, int row0, void* stream);
+int rave_model_set_speaker_row0(rave_model* m, int row0);
+/* out[0..2] = speaker_rows, the mode (0 shared, 1 per-row), speaker_row0 */
+int rave_model_speaker_info(const rave_model* m, int32_t* out3);
 int rave_model_adain_count(const rave_model* m);
 /* module i: name, channels, and its buffers copied out / in (host, synchronous):
  * stats (4, max_batch, C) = mean_x, std_x, mean_y, std_y; counters[2] =
@@ -947,7 +978,7 @@ int rave_stream_delay(const rave_stream* s);
  * nodes of the captured graph (RAVE_STREAM_GRAPH; the copies around a replay are
  * not counted: the call copies the block's input straight into the history
  * buffer and the output out of a staging buffer, and fills the latents' speaker
- * channels outside the graph once per rave_model_set_speaker) or the plan's
+ * channels outside the graph once per rave_model_set_speaker*) or the plan's
  * launches (eager:
  * one per op, a run of history shifts batched into one launch as rave_plan_run
  * issues it).  Negative = status. */

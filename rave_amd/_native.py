@@ -42,7 +42,7 @@ OP_UNIT = 11
 OP_STACK = 12
 OP_HEAD = 13
 OP_TAIL = 14
-ABI_VERSION = 20
+ABI_VERSION = 21
 SPLITK_TICKETS = 4096       # RAVE_SPLITK_TICKETS: zeroed int32 counters at the head of a split-K workspace
 SPLITK_STATUS_WORD = SPLITK_TICKETS - 1   # RAVE_SPLITK_STATUS_WORD: the cooperative unit's give-up word
 
@@ -92,7 +92,8 @@ class SynthesisArgs(C.Structure):
 
 
 class FillArgs(C.Structure):
-    _fields_ = [("batch", i32), ("channels", i32), ("t_len", i32), ("_pad0", i32),
+    # values_sb: row stride of `values` (0: one vector broadcast to every batch row)
+    _fields_ = [("batch", i32), ("channels", i32), ("t_len", i32), ("values_sb", i32),
                 ("y", vp), ("y_sb", i64), ("y_sc", i64), ("values", vp)]
 
 
@@ -192,7 +193,7 @@ class EdgeArgs(C.Structure):
                 ("x", vp), ("x_sb", i64), ("x_sc", i64), ("y", vp), ("y_sb", i64), ("y_sc", i64),
                 ("weight", vp), ("bias", vp), ("alpha", vp), ("filter", vp),
                 ("noise", vp), ("n_sb", i64), ("n_sc", i64),
-                ("fill_y", vp), ("f_sb", i64), ("f_sc", i64), ("fill_values", vp)]
+                ("fill_y", vp), ("f_sb", i64), ("f_sc", i64), ("fill_values", vp), ("fill_vs", i64)]
 
 
 STFT_MAX_SCALES = 8          # RAVE_STFT_MAX_SCALES
@@ -236,7 +237,7 @@ class ModelConfig(C.Structure):
                 ("leaky_slope", f32), ("conv_bias", i32), ("convt_bias", i32),
                 ("noise", i32), ("noise_hidden", i32), ("noise_bands", i32), ("n_noise_ratios", i32),
                 ("noise_ratios", i32 * MAX_RATIOS), ("rvq_quantizers", i32), ("rvq_codebook_size", i32),
-                ("fuse_units", i32)]
+                ("fuse_units", i32), ("speaker_rows", i32)]
 
 
 class Param(C.Structure):
@@ -283,7 +284,7 @@ EXPORTS = [
     "rave_model_param_count", "rave_model_param_info", "rave_model_create", "rave_model_destroy",
     "rave_model_encode", "rave_model_decode", "rave_model_forward", "rave_model_encode_codes",
     "rave_model_decode_codes", "rave_model_noise_shape", "rave_model_adain_control", "rave_model_set_row0",
-    "rave_model_set_speaker",
+    "rave_model_set_speaker", "rave_model_set_speakers", "rave_model_set_speaker_row0", "rave_model_speaker_info",
     "rave_model_adain_count", "rave_model_adain_info", "rave_model_adain_get", "rave_model_adain_set",
     "rave_model_tuning_get", "rave_model_tuning_set", "rave_model_plan_ops", "rave_model_profile",
     "rave_model_op_times", "rave_stream_create", "rave_stream_destroy", "rave_stream_reset",
@@ -392,6 +393,9 @@ def _load():
     lib.rave_model_adain_control.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]
     lib.rave_model_set_row0.argtypes = [vp, C.c_int]
     lib.rave_model_set_speaker.argtypes = [vp, vp, vp]
+    lib.rave_model_set_speakers.argtypes = [vp, vp, C.c_int, C.c_int, vp]
+    lib.rave_model_set_speaker_row0.argtypes = [vp, C.c_int]
+    lib.rave_model_speaker_info.argtypes = [vp, C.POINTER(i32)]
     lib.rave_model_adain_count.argtypes = [vp]
     lib.rave_model_adain_info.argtypes = [vp, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int),
                                           C.POINTER(C.c_int)]
@@ -427,9 +431,16 @@ def _load():
 lib = _load()
 
 
-def model_config(cfg) -> ModelConfig:
-    """rave_amd.config.RaveConfig -> the engine's rave_model_config."""
+SPEAKER_ROWS = 64           # the engine's default table rows (speaker_rows 0; the reference's cc.MAX_BATCH_SIZE)
+
+
+def model_config(cfg, speaker_rows: int = 0) -> ModelConfig:
+    """rave_amd.config.RaveConfig -> the engine's rave_model_config.
+    ``speaker_rows``: rows of the per-row speaker table (0: SPEAKER_ROWS)."""
     c = ModelConfig()
+    if speaker_rows < 0:
+        raise ValueError("speaker_rows must be >= 0")
+    c.speaker_rows = int(speaker_rows)
     c.n_band, c.enc_bands, c.capacity = cfg.n_band, cfg.enc_bands, cfg.capacity
     c.latent_size, c.kernel_size, c.speaker_size = cfg.latent_size, cfg.kernel_size, cfg.speaker_size
     if len(cfg.ratios) > MAX_RATIOS or len(cfg.dilations) != len(cfg.ratios):

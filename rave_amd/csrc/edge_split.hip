@@ -191,11 +191,14 @@ __global__ __launch_bounds__(kEdgeNT) void encoder_head_kernel(rave_edge_args a,
     const int n0 = tile * kHF;
     if (a.fill_channels > 0) {
         // the speaker concat of RAVE.encode: the batch item's tiles share its rows
+        // (fill_vs 0: one vector for all; else row b of a table -- a uniform base,
+        // so the per-row form costs scalar arithmetic only)
         float* z = a.fill_y + (int64_t)b * a.f_sb;
+        const float* fv = a.fill_values + (int64_t)b * a.fill_vs;
         const int n = a.fill_channels * a.fill_t;
         for (int i = tile * kEdgeNT + tid; i < n; i += tiles * kEdgeNT) {
             const int c = i / a.fill_t, t = i - c * a.fill_t;
-            z[(int64_t)c * a.f_sc + t] = a.fill_values[c];
+            z[(int64_t)c * a.f_sc + t] = fv[c];
         }
     }
     const int F = a.frames;
@@ -1050,6 +1053,8 @@ extern "C" int rave_encoder_head(const rave_edge_args* p, void* stream) {
     }
     RAVE_CHECK_ARG(a.fill_channels == 0 || (a.fill_y && a.fill_values && a.fill_t > 0),
                    "encoder_head: fill needs fill_y, fill_values and fill_t");
+    RAVE_CHECK_ARG(a.fill_channels == 0 || a.fill_vs == 0 || a.fill_vs >= a.fill_channels,
+                   "encoder_head: fill_vs must be 0 (one shared vector) or >= fill_channels");
     if (a.act != RAVE_ACT_NONE) {   // EncoderV2's first conv has no input activation (rave/blocks.py:533-536)
         set_error("encoder_head: the fused analysis + first conv applies no input activation (act must be RAVE_ACT_NONE)");
         return RAVE_ERR_UNSUPPORTED;

@@ -20,6 +20,7 @@
 #include <cstdlib>
 
 #include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstring>
 #include <functional>
@@ -52,6 +53,7 @@ static void check_config(const rave_model_config& c) {
     auto bad = [](const std::string& m) { fail(RAVE_ERR_ARG, "model config: " + m); };
     if (c.n_band <= 0 || c.enc_bands <= 0 || c.enc_bands > c.n_band) bad("n_band / enc_bands");
     if (c.capacity <= 0 || c.latent_size <= 0 || c.kernel_size <= 0 || c.speaker_size < 0) bad("sizes");
+    if (c.speaker_rows < 0) bad("speaker_rows");
     if (c.n_ratios <= 0 || c.n_ratios > RAVE_MAX_RATIOS) bad("n_ratios");
     for (int i = 0; i < c.n_ratios; ++i) {
         if (c.ratios[i] <= 0) bad("ratios");
@@ -351,7 +353,18 @@ struct Model {
     std::map<std::string, int> ad_index;
     bool learn_x = false, learn_y = false, touched = false;
     int row0 = 0;
-    int spk_version = 0;               // bumped by rave_model_set_speaker (stream graphs refill)
+    // speaker conditioning: the shared vector at spk_off, and a table of spk_rows
+    // x speaker_size floats at spk_tbl_off.  Per-row mode: batch row b reads table
+    // row spk_row0 + b.  Plans are built in the shared form; sync_speaker patches
+    // their fill sites to the model's current (mode, row0).
+    int64_t spk_tbl_off = 0;
+    int spk_rows = 0, spk_row0 = 0;
+    bool spk_per_row = false;
+    // bumped by every value, mode or row0 change (stream graphs refill); atomic:
+    // a setter and a stream block may run on different host threads
+    std::atomic<int> spk_version{0};
+    void check_speaker_rows(int B, const char* what) const;
+    bool sync_speaker(Plan& p);
     // autotuner choices: key -> (choice, ms)
     std::map<std::string, std::pair<int64_t, double>> tuned;
     std::map<std::string, std::unique_ptr<Plan>> plans;
@@ -1214,6 +1227,45 @@ void Model::synthesis_op(Plan& p, int B, int F, const View& x, const View& y, co
     o.bytes = 4.0 * (2.0 * B * F * cfg.n_band + (noise ? (double)B * F * cfg.n_band : 0.0));
 }
 
+// A call of B batch rows in per-row mode reads table rows [spk_row0, spk_row0 + B)
+void Model::check_speaker_rows(int B, const char* what) const {
+    if (!spk_per_row || cfg.speaker_size == 0) return;
+    if ((int64_t)spk_row0 + B > spk_rows)
+        fail(RAVE_ERR_ARG, std::string(what) + ": the speaker table holds " + std::to_string(spk_rows) +
+                               " rows; batch " + std::to_string(B) + " at speaker_row0 " +
+                               std::to_string(spk_row0) + " exceeds them");
+}
+
+// Every site of a plan that writes speaker channels (the fill op, the fill
+// fused into the encoder head) carries the values' base and row stride in its
+// arguments.  Plans are built in the shared form (stride 0, the vector at
+// spk_off); when the model's mode or row0 differs from what the plan last ran
+// with, patch those two fields -- the plan, its workspace and every other op
+// stay what they were.  Returns whether an op was patched (a stream re-captures).
+bool Model::sync_speaker(Plan& p) {
+    const int stride = spk_per_row ? cfg.speaker_size : 0;
+    const int row0 = spk_per_row ? spk_row0 : 0;
+    if (p.spk_stride == stride && p.spk_row0 == row0) return false;
+    const float* base = spk_per_row ? arena + spk_tbl_off + (int64_t)row0 * cfg.speaker_size : arena + spk_off;
+    bool any = false;
+    for (int i = 0; i < (int)p.ops.size(); ++i) {
+        if (p.ops[i].kind == RAVE_OP_FILL) {
+            const int32_t vs = stride;
+            check_rc(plan_patch(p.handle, i, (int)offsetof(rave_fill_args, values_sb), &vs, 4), "plan_patch");
+            check_rc(plan_patch(p.handle, i, (int)offsetof(rave_fill_args, values), &base, 8), "plan_patch");
+            any = true;
+        } else if (p.ops[i].kind == RAVE_OP_HEAD && p.ops[i].op.u.edge.fill_channels > 0) {
+            const int64_t vs = stride;
+            check_rc(plan_patch(p.handle, i, (int)offsetof(rave_edge_args, fill_vs), &vs, 8), "plan_patch");
+            check_rc(plan_patch(p.handle, i, (int)offsetof(rave_edge_args, fill_values), &base, 8), "plan_patch");
+            any = true;
+        }
+    }
+    p.spk_stride = stride;
+    p.spk_row0 = row0;
+    return any;
+}
+
 void Model::fill_speaker(Plan& p, int B, int Fz, const View& z) {
     if (cfg.speaker_size == 0) return;
     rave_fill_args a{};
@@ -1685,7 +1737,10 @@ Plan& Model::plan_of(int which, int B, int T) {
 // One call of a plan kind over `batch` items: I/O slot 0 = in, 1 = out, 2 = noise.
 void Model::run_kind(int which, int batch, int t, const void* in, void* out, const float* noise, hipStream_t st) {
     cur_stream = st;
+    const bool spk = (which == 0 || which == 3) && cfg.speaker_size > 0;   // the plans that write speaker channels
+    if (spk) check_speaker_rows(batch, "speaker");    // before any launch (plan building times kernels)
     Plan& p = plan_of(which, batch, t);
+    if (spk) sync_speaker(p);
     void* slots[3] = {(void*)in, out, (void*)noise};
     p.run(slots, (which == 1 || which == 3) && cfg.noise ? 3 : 2, st);
 }
@@ -1865,6 +1920,11 @@ static Model* create_model(const rave_model_config& cfg, const rave_param* param
             cbs.insert(cbs.end(), e, e + (int64_t)cfg.rvq_codebook_size * cfg.latent_size);
         }
         m->cb_off = m->add(cbs);
+    }
+    // the per-row speaker table, zeroed, behind everything else (no other offset moves)
+    if (cfg.speaker_size > 0) {
+        m->spk_rows = cfg.speaker_rows > 0 ? cfg.speaker_rows : 64;
+        m->spk_tbl_off = m->add(std::vector<float>((size_t)m->spk_rows * cfg.speaker_size, 0.f));
     }
     RAVE_HIP_OR_THROW(hipMalloc(&m->arena, std::max<size_t>(m->host.size(), 64) * 4));
     RAVE_HIP_OR_THROW(hipMemcpy(m->arena, m->host.data(), m->host.size() * 4, hipMemcpyHostToDevice));
@@ -2123,7 +2183,48 @@ extern "C" int rave_model_set_speaker(rave_model* h, const float* speaker, void*
         // before every later encode/decode (and streaming graph replay) on it
         RAVE_HIP_OR_THROW(hipMemcpyAsync(m->arena + m->spk_off, speaker, sizeof(float) * m->cfg.speaker_size,
                                          hipMemcpyDefault, as_stream(stream)));
+        m->spk_per_row = false;
         ++m->spk_version;
+    });
+}
+
+extern "C" int rave_model_set_speakers(rave_model* h, const float* emb, int rows, int row0, void* stream) {
+    return guarded([&] {
+        Model* m = model_of(h);
+        if (!emb) fail(RAVE_ERR_ARG, "set_speakers: null embeddings");
+        if (m->cfg.speaker_size == 0) fail(RAVE_ERR_ARG, "set_speakers: the model has no speaker channels");
+        if (rows <= 0 || row0 < 0 || (int64_t)row0 + rows > m->spk_rows)
+            fail(RAVE_ERR_ARG, "set_speakers: rows [" + std::to_string(row0) + ", " +
+                                   std::to_string((int64_t)row0 + rows) + ") do not fit the speaker table's " +
+                                   std::to_string(m->spk_rows) + " rows");
+        const int64_t S = m->cfg.speaker_size;
+        // host or device source, ordered on the caller's stream like set_speaker
+        RAVE_HIP_OR_THROW(hipMemcpyAsync(m->arena + m->spk_tbl_off + row0 * S, emb, sizeof(float) * rows * S,
+                                         hipMemcpyDefault, as_stream(stream)));
+        m->spk_per_row = true;
+        ++m->spk_version;
+    });
+}
+
+extern "C" int rave_model_set_speaker_row0(rave_model* h, int row0) {
+    return guarded([&] {
+        Model* m = model_of(h);
+        if (m->cfg.speaker_size == 0) fail(RAVE_ERR_ARG, "set_speaker_row0: the model has no speaker channels");
+        if (row0 < 0 || row0 >= m->spk_rows)
+            fail(RAVE_ERR_ARG, "speaker_row0 must be in [0, " + std::to_string(m->spk_rows) + ")");
+        if (row0 == m->spk_row0) return;
+        m->spk_row0 = row0;
+        ++m->spk_version;
+    });
+}
+
+extern "C" int rave_model_speaker_info(const rave_model* h, int32_t* out3) {
+    return guarded([&] {
+        const Model* m = model_of(const_cast<rave_model*>(h));
+        if (!out3) fail(RAVE_ERR_ARG, "null output");
+        out3[0] = m->spk_rows;
+        out3[1] = m->spk_per_row ? 1 : 0;
+        out3[2] = m->spk_row0;
     });
 }
 
@@ -2672,6 +2773,23 @@ static void sync_adain(Stream& s) {
     if (s.flags & RAVE_STREAM_GRAPH) recapture(s);
 }
 
+// The speaker fill sites of the stream's plans follow the model's mode and row0
+// (Model::sync_speaker).  Graph mode: the encoder's fill that runs outside the
+// graph (enc_fill) only needs to run again; a fill captured inside a graph
+// carries its arguments in the graph, so that graph is captured again.
+static void sync_stream_speaker(Stream& s) {
+    Model* m = s.m;
+    if (m->cfg.speaker_size == 0) return;
+    m->check_speaker_rows(s.B, "stream");
+    bool again = false;
+    if (s.has_enc() && m->sync_speaker(*s.enc)) {
+        if (s.enc_fill >= 0) s.spk_seen = -1;
+        else again = true;
+    }
+    if (s.has_dec() && m->sync_speaker(*s.dec)) again = true;
+    if (again && (s.flags & RAVE_STREAM_GRAPH) && s.cap) recapture(s);
+}
+
 }  // namespace rave
 
 struct rave_stream {
@@ -2802,6 +2920,7 @@ static void direct_copy(const Stream::Direct& d, const void* src, hipStream_t st
 static void stream_enc(Stream* s, const void* x, void* out, hipStream_t st) {
     if (!s->has_enc()) fail(RAVE_ERR_STATE, "stream was created RAVE_STREAM_DECODE_ONLY");
     sync_adain(*s);
+    sync_stream_speaker(*s);
     if (s->flags & RAVE_STREAM_GRAPH) {
         if (s->enc_in.dst) direct_copy(s->enc_in, x, st);
         else RAVE_HIP_OR_THROW(hipMemcpyAsync(s->x_st, x, (size_t)s->B * s->block * 4, hipMemcpyDeviceToDevice, st));
@@ -2822,6 +2941,7 @@ static void stream_enc(Stream* s, const void* x, void* out, hipStream_t st) {
 static void stream_dec(Stream* s, const void* in, float* y, const float* noise_u, hipStream_t st) {
     if (!s->has_dec()) fail(RAVE_ERR_STATE, "stream was created RAVE_STREAM_ENCODE_ONLY");
     sync_adain(*s);
+    sync_stream_speaker(*s);
     Model* m = s->m;
     const int64_t nu = noise_count(*s);
     const float* u = nullptr;

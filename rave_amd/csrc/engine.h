@@ -136,6 +136,9 @@ struct Plan {
     void* ws_dev = nullptr;
     int64_t ws_floats = 0;
     rave_plan* handle = nullptr;
+    // what the speaker fill sites currently carry (Model::sync_speaker): the
+    // values' row stride (0: the shared vector) and the first table row
+    int spk_stride = 0, spk_row0 = 0;
     ~Plan();
     template <typename A>
     PlanOp& add(int kind, const A& args, const std::string& label) {
@@ -197,7 +200,7 @@ struct Stream {
     } enc_in, dec_in;
     // graph mode: the encoder plan's speaker fill (op index, -1: none) writes the
     // constant speaker channels of the staged latents; it runs outside the graph,
-    // once per speaker (Model::spk_version)
+    // once per speaker value, mode or row0 (Model::spk_version)
     int enc_fill = -1, spk_seen = -1;
     int delay = 0;
     int ad_mode = -1;                              // AdaIN mode baked into the plans

@@ -13,11 +13,13 @@ namespace rave {
 __global__ void fill_channels_kernel(rave_fill_args a) {
     const int64_t total = (int64_t)a.channels * a.t_len;
     const int b = blockIdx.y;
+    // the row's values: a uniform base (values_sb 0: the one shared vector)
+    const float* v = a.values + (int64_t)b * a.values_sb;
     for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total;
          i += (int64_t)gridDim.x * blockDim.x) {
         int c = (int)(i / a.t_len);
         int t = (int)(i - (int64_t)c * a.t_len);
-        a.y[(int64_t)b * a.y_sb + (int64_t)c * a.y_sc + t] = a.values[c];
+        a.y[(int64_t)b * a.y_sb + (int64_t)c * a.y_sc + t] = v[c];
     }
 }
 
@@ -341,6 +343,8 @@ extern "C" int rave_fill_uniform(float* y, int64_t n, uint64_t seed, float lo, f
 extern "C" int rave_fill_channels(const rave_fill_args* p, void* stream) {
     RAVE_CHECK_ARG(p && p->y && p->values, "fill_channels: null pointer");
     RAVE_CHECK_ARG(p->batch > 0 && p->channels > 0 && p->t_len > 0, "fill_channels: empty shape");
+    RAVE_CHECK_ARG(p->values_sb == 0 || p->values_sb >= p->channels,
+                   "fill_channels: values_sb must be 0 (one shared vector) or >= channels");
     int64_t total = (int64_t)p->channels * p->t_len;
     int blocks = (int)std::min<int64_t>(ceil_div64(total, 256), 1024);
     launch(fill_channels_kernel, dim3(blocks, p->batch), dim3(256), 0, as_stream(stream), *p);

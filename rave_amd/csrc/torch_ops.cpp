@@ -225,9 +225,18 @@ struct Engine : torch::CustomClassHolder {
         check(rave_model_adain_control(m, (int)learn_x, (int)learn_y, reset_x, reset_y, cur()), "adain_control");
     }
     // the constant speaker embedding encode concatenates (nn~ `speaker` choice)
+    // 2-D (R, speaker_size): per-row mode, batch row b reads row b (rave_model_set_speakers
+    // at row 0).  The table is run-time state: the pickle keeps the shared vector.
     void set_speaker(at::Tensor emb) {
-        TORCH_CHECK_VALUE(emb.numel() == cfg.speaker_size, "speaker embedding must have ", cfg.speaker_size, " values");
         c10::hip::HIPGuard g((c10::DeviceIndex)device);
+        if (emb.dim() == 2) {
+            TORCH_CHECK_VALUE(emb.size(0) > 0 && emb.size(1) == cfg.speaker_size, "speaker embeddings must be (R, ",
+                              cfg.speaker_size, ")");
+            at::Tensor rows = emb.detach().to(at::Device(at::kCUDA, device), at::kFloat).contiguous();
+            check(rave_model_set_speakers(m, rows.data_ptr<float>(), (int)rows.size(0), 0, cur()), "set_speakers");
+            return;
+        }
+        TORCH_CHECK_VALUE(emb.numel() == cfg.speaker_size, "speaker embedding must have ", cfg.speaker_size, " values");
         at::Tensor src = emb.detach().to(at::Device(at::kCUDA, device), at::kFloat).contiguous();
         check(rave_model_set_speaker(m, src.data_ptr<float>(), cur()), "set_speaker");
         // src came from torch's caching allocator on this stream, so freeing it on

@@ -177,6 +177,10 @@ class ShardedRunner:
         if getattr(self.model, "adain", None) is not None:
             # AdaIN buffer rows follow the global batch index (rave/blocks.py:886-891)
             self.model.adain_row0 = sum(sizes[:rank])
+        if getattr(self.model, "per_row_speakers", False):
+            # per-row speakers: the table is filled identically on every rank and
+            # indexed by the global batch row, like the AdaIN buffers
+            self.model.speaker_row0 = sum(sizes[:rank])
         if self.mode == "codes":
             t = self.model.encode_codes(x_local)
             return self._gather(t, sizes), self.model.decode_codes(t)

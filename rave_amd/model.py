@@ -41,6 +41,37 @@ def _stream(dev: torch.device) -> C.c_void_p:
     return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
+def speaker_arg(embedding, speaker_size: int, speaker_rows: int, row0: int = 0):
+    """Validate a ``set_speaker`` argument without touching the device.
+    Returns ``("shared", values)`` for a 1-D embedding or ``("rows", values)``
+    for a 2-D ``(R, speaker_size)`` one; ``values`` is a float32 tensor (torch
+    input; a 2-D one must be float32 already) or a contiguous float32 numpy array.  Raises
+    ``ValueError`` for another rank, a wrong width, a tensor of another dtype,
+    or rows ``[row0, row0 + R)`` that do not fit ``speaker_rows``."""
+    if isinstance(embedding, torch.Tensor):
+        # the table takes a tensor as it is (the device hand-off makes no converted
+        # copy); the shared vector keeps converting, as it always has
+        if embedding.dim() == 2 and embedding.dtype != torch.float32:
+            raise ValueError(f"an (R, {speaker_size}) speaker tensor must be float32, got {embedding.dtype}")
+        src = embedding.detach().to(torch.float32)
+    else:
+        src = np.array(embedding, dtype=np.float32, order="C")     # a copy: writable, whatever the caller holds
+    shape = tuple(src.shape)
+    if len(shape) == 1:
+        if shape[0] != speaker_size:
+            raise ValueError(f"speaker embedding must have {speaker_size} values, got {shape[0]}")
+        if row0 != 0:
+            raise ValueError("row0 applies to (R, speaker_size) embeddings only")
+        return "shared", src
+    if len(shape) != 2:
+        raise ValueError(f"speaker embedding must be ({speaker_size},) or (R, {speaker_size}), got {shape}")
+    if shape[1] != speaker_size or shape[0] < 1:
+        raise ValueError(f"speaker embeddings must be (R >= 1, {speaker_size}), got {shape}")
+    if row0 < 0 or row0 + shape[0] > speaker_rows:
+        raise ValueError(f"speaker rows [{row0}, {row0 + shape[0]}) do not fit the table's {speaker_rows} rows")
+    return "rows", src
+
+
 class RAVE:
     """HIP implementation of RAVE.encode / decode / forward for one config.
 
@@ -50,13 +81,20 @@ class RAVE:
     fp32 on every op, launch configurations and fused units timed as in auto), or
     "f32_bf3" (as f32_tuned, with the fused units also timed in bf16x3: fp32 on
     the bf16 matrix cores with an exact three-way operand split).  ``tuning`` replays the
-    choices of an earlier model's ``tuning()`` without timing runs."""
+    choices of an earlier model's ``tuning()`` without timing runs.
+    ``speaker_rows``: rows of the per-row speaker table (``set_speaker`` with
+    ``(R, speaker_size)`` embeddings); the default is the reference's
+    ``cc.MAX_BATCH_SIZE``."""
 
     def __init__(self, cfg: RaveConfig, params: Mapping[str, np.ndarray], speaker: np.ndarray,
                  device=None, hk: Optional[np.ndarray] = None,
                  adain_stats: Optional[Mapping] = None, fuse_units: bool = True,
-                 precision: str = "f32", tuning: Optional[list] = None):
+                 precision: str = "f32", tuning: Optional[list] = None, speaker_rows: int = N.SPEAKER_ROWS):
         check_params(cfg, params)
+        if int(speaker_rows) < 1:
+            raise ValueError("speaker_rows must be >= 1")
+        self.speaker_rows = int(speaker_rows)      # rows of the per-row speaker table (set_speaker, 2-D)
+        self._spk_row0 = 0
         modes = {"auto": N.PREC_AUTO, "f32_tuned": N.PREC_F32_TUNED, "f32_bf3": N.PREC_F32_BF3,
                  "f32": N.PREC_F32, "split16": N.PREC_SPLIT16}
         if precision not in modes:
@@ -74,7 +112,7 @@ class RAVE:
         spk = np.ascontiguousarray(np.asarray(speaker, np.float32).reshape(-1))
         if spk.size != cfg.speaker_size:
             raise ValueError(f"speaker embedding must have {cfg.speaker_size} values")
-        ccfg = N.model_config(cfg)
+        ccfg = N.model_config(cfg, self.speaker_rows)
         ccfg.fuse_units = int(fuse_units)
         keep = []
         plist = []
@@ -138,25 +176,68 @@ class RAVE:
         N.check(N.lib.rave_model_tuning_set(self.handle, text.encode()), "tuning_set")
 
     # ------------------------------------------------------------ speaker
-    def set_speaker(self, embedding) -> None:
-        """Replace the constant speaker embedding that encode / decode_codes
-        concatenate (rave/model.py:617-618; the nn~ `speaker` choice among
-        embeddings, scripts/export.py:384-396).  ``embedding``: speaker_size
-        values, numpy or a torch tensor (e.g. ``SpeakerRAVE.embed`` output on
-        this device).  Ordered on the current stream before later calls."""
-        if isinstance(embedding, torch.Tensor):
-            src = embedding.detach().to(self.device, torch.float32).contiguous().reshape(-1)
-            if src.numel() != self.cfg.speaker_size:
-                raise ValueError(f"speaker embedding must have {self.cfg.speaker_size} values")
-            N.check(N.lib.rave_model_set_speaker(self.handle, src.data_ptr(), _stream(self.device)), "set_speaker")
-            self._spk_keep = src          # the copy is asynchronous
-            return
-        spk = np.ascontiguousarray(np.asarray(embedding, np.float32).reshape(-1))
-        if spk.size != self.cfg.speaker_size:
-            raise ValueError(f"speaker embedding must have {self.cfg.speaker_size} values")
-        src = torch.from_numpy(spk).to(self.device)
-        N.check(N.lib.rave_model_set_speaker(self.handle, src.data_ptr(), _stream(self.device)), "set_speaker")
-        self._spk_keep = src
+    def set_speaker(self, embedding, row0: int = 0) -> None:
+        """Set the speaker embedding that encode / decode_codes concatenate
+        (rave/model.py:617-618), numpy or a torch tensor.
+
+        * 1-D, ``speaker_size`` values: **shared** mode -- every batch row of
+          every call reads this one vector (the nn~ `speaker` choice among
+          embeddings, scripts/export.py:384-396).
+        * 2-D ``(R, speaker_size)``: **per-row** mode -- writes rows
+          ``[row0, row0 + R)`` of the model's ``speaker_rows``-row table; batch
+          row ``b`` of every later call reads table row ``speaker_row0 + b`` (the
+          reference's per-clip embedding, rave/model.py:669-675, 714-729).  A
+          float32 tensor on this device (``SpeakerRAVE.embed(x)``) is copied
+          device-to-device on the current stream, with no host synchronisation.
+
+        Ordered on the current stream: later calls (and streaming blocks) on
+        that stream, or on one that waits on it, see the new values."""
+        kind, src = speaker_arg(embedding, self.cfg.speaker_size, self.speaker_rows, row0)
+        if isinstance(src, torch.Tensor):
+            src = src.to(self.device).contiguous()      # no copy for a contiguous tensor on this device
+        else:
+            src = torch.from_numpy(src).to(self.device)
+        with torch.cuda.device(self.device):
+            if kind == "shared":
+                N.check(N.lib.rave_model_set_speaker(self.handle, src.data_ptr(), _stream(self.device)), "set_speaker")
+            else:
+                N.check(N.lib.rave_model_set_speakers(self.handle, src.data_ptr(), int(src.shape[0]), int(row0),
+                                                      _stream(self.device)), "set_speakers")
+        self._spk_keep = src          # the copy is asynchronous
+
+    @property
+    def speaker_row0(self) -> int:
+        """Per-row mode: the table row batch row 0 reads (a data-parallel
+        shard's first row of a table filled identically on every rank)."""
+        return self._spk_row0
+
+    @speaker_row0.setter
+    def speaker_row0(self, v: int) -> None:
+        N.check(N.lib.rave_model_set_speaker_row0(self.handle, int(v)), "set_speaker_row0")
+        self._spk_row0 = int(v)
+
+    @property
+    def per_row_speakers(self) -> bool:
+        """Whether the model is in per-row speaker mode (rave_model_speaker_info)."""
+        out = (N.i32 * 3)()
+        N.check(N.lib.rave_model_speaker_info(self.handle, out), "speaker_info")
+        return bool(out[1])
+
+    def convert(self, x: torch.Tensor, target, noise_u: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Voice conversion of a whole batch, the conversion half of the
+        reference's ``validation_step`` (rave/model.py:714-729): row ``b`` of
+        ``x`` is decoded with target ``b``'s embedding.  ``target``: embeddings
+        ``(B, speaker_size)``, or ``(speaker_encoder, audio)`` with a
+        ``SpeakerRAVE`` and target audio ``(B, 1, T')`` that it embeds.  Leaves
+        the model in per-row mode with these rows at ``speaker_row0``."""
+        B, _ = self._check_audio(x)
+        if isinstance(target, tuple):
+            enc, audio = target
+            target = enc.embed(audio)
+        if tuple(target.shape) != (B, self.cfg.speaker_size):
+            raise ValueError(f"target embeddings must be ({B}, {self.cfg.speaker_size}), got {tuple(target.shape)}")
+        self.set_speaker(target, row0=self.speaker_row0)
+        return self.forward(x, noise_u)
 
     # ------------------------------------------------------------ AdaIN rows
     @property
@@ -282,14 +363,18 @@ class RAVE:
             N.check(N.lib.rave_pqmf_synthesis(C.byref(syn), _stream(x.device)), "pqmf_synthesis")
         return y
 
-    def validate(self, x: torch.Tensor, noise_u: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+    def validate(self, x: torch.Tensor, noise_u: Optional[torch.Tensor] = None,
+                 speaker_encoder=None) -> Dict[str, torch.Tensor]:
         """The metric of ``RAVE.validation_step`` (rave/model.py:636-686):
         ``audio_distance(pqmf.inverse(pqmf(x)), forward(x))`` with the config's
         ``log_epsilon``, as ``{'spectral_distance': 0-dim device tensor}``.
 
-        The reference embeds each clip with its SpeakerRAVE first; this uses the
-        model's current speaker embedding, so callers who want the reference's
-        behaviour call ``set_speaker`` (e.g. with ``SpeakerRAVE.embed(x)``) before."""
+        With ``speaker_encoder`` (a ``SpeakerRAVE``) every clip is embedded first
+        and decoded with its own embedding, as the reference does
+        (rave/model.py:669-681); the model is left in per-row mode with these
+        embeddings.  Without one, the model's current speaker state is used."""
+        if speaker_encoder is not None:
+            self.set_speaker(speaker_encoder.embed(x), row0=self.speaker_row0)
         return self._distance(self.pqmf_roundtrip(x), self.forward(x, noise_u))
 
     def encode_codes(self, x: torch.Tensor) -> torch.Tensor:

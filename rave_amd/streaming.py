@@ -66,6 +66,16 @@ class StreamingRAVE:
         """Zero every cache (the reference's freshly created CachedPadding1d)."""
         N.check(N.lib.rave_stream_reset(self.handle, _stream(self.model.device)), "stream_reset")
 
+    def set_speaker(self, embedding, row0: int = 0) -> None:
+        """The voice of the following blocks: one ``speaker_size`` vector for
+        every stream of the batch, or ``(R, speaker_size)`` rows of the model's
+        speaker table so that stream ``b`` reads row ``speaker_row0 + b``
+        (``RAVE.set_speaker``; e.g. ``set_speaker(e[None], row0=b)`` switches
+        stream ``b`` alone).  The engine keeps the speaker state on the model,
+        so this is the model's call: every stream of the model follows it from
+        its next block, when that block runs on the stream the call was made on."""
+        self.model.set_speaker(embedding, row0)
+
     def encode(self, x: torch.Tensor) -> torch.Tensor:
         if tuple(x.shape) != (self.B, 1, self.block) or x.dtype != torch.float32 or x.device.type != "cuda":
             raise ValueError(f"x must be a float32 CUDA tensor of shape {(self.B, 1, self.block)}")
