@@ -706,6 +706,78 @@ typedef struct rave_distance_args {
 int64_t rave_audio_distance_workspace(const rave_distance_args* a);
 int rave_audio_distance(const rave_distance_args* a, void* stream);
 
+/* ================================================================ differentiable spectral losses
+ * The spectral training losses with their gradient with respect to the value
+ * signal (csrc/stft_loss.hip): MultiResolutionSTFTLoss (rave/stft_loss.py:12-144,
+ * the loss RAVE.training_step uses, rave/model.py:191-198) and AudioDistanceV1
+ * (above).  The target is a constant; no gradient flows to it.
+ *
+ * Frame geometry, per resolution (n_fft, hop, win): torch.stft(x, n_fft, hop,
+ * win, window=hann_window(win)) with its defaults -- center=True with reflect
+ * padding of n_fft/2 (t_len > n_fft/2), the periodic Hann window of length win
+ * placed at offset (n_fft - win) / 2 of the FFT buffer and zeros around it,
+ * 1 + t_len / hop frames, onesided, not normalised.  n_fft: a power of two in
+ * [64, 4096]; 1 <= hop; 1 <= win <= n_fft.  AudioDistanceV1's geometry is
+ * (n, n/4, n).
+ *
+ * Tables: rave_stft_loss_pack_table(n_fft, win, out) writes, in float64 rounded
+ * once, rave_stft_loss_table_size(n_fft, win) = 2 n_fft + win floats:
+ *   out[2k], out[2k+1] = cos(2 pi k / n_fft), -sin(2 pi k / n_fft)   k in [0, n_fft)
+ *   out[2 n_fft + i]   = 0.5 - 0.5 cos(2 pi i / win)                 i in [0, win)
+ *
+ * Forward.  Frame f of the value is the real part and frame f of the target the
+ * imaginary part of one complex FFT.  With V, T the two magnitudes per bin:
+ *   RAVE_STFT_LOSS_MULTIRES  V = sqrt(max(|.|^2, 1e-7)), likewise T;
+ *     sc_r  = sqrt(sum (T - V)^2) / sqrt(sum T^2),  mag_r = mean |log T - log V|
+ *     out[0] = mean_r sc_r, out[1] = mean_r mag_r, out[2 + 2r] = sc_r, out[3 + 2r] = mag_r
+ *   RAVE_STFT_LOSS_V1  lin_r = sum (T - V)^2 / sum T^2,
+ *     log_r = mean |log(T + eps) - log(V + eps)|
+ *     out[0] = sum_r (lin_r + log_r), out[1] = 0, out[2 + 2r] = lin_r, out[3 + 2r] = log_r
+ * (2 + 2 n_res floats).  Every workgroup leaves three partial sums in its own
+ * workspace slot; a one-workgroup finalize adds them in double in a fixed order
+ * and leaves, per resolution, {sum (T-V)^2, sum T^2, c_lin, c_log} in `saved`
+ * (4 n_res floats; c_lin, c_log: the loss's derivative with respect to the two
+ * per-bin terms, formed in double).  No atomics; results are bit-reproducible.
+ *
+ * Backward.  grad_value (rows, t_len) = d (sum_i grad_out[i] out[i]) / d value,
+ * grad_out being device floats read by the kernel (two for MULTIRES, one for
+ * V1).  Per frame the FFT is redone, the per-bin weight w = dL/dV formed from
+ * `saved`, G = w * spectrum / V for bins 0..n_fft/2 (zero where the multires
+ * clamp is active, or V = 0 for V1), and the real part of the unnormalised
+ * inverse DFT of G times the window written to the workspace; a second kernel
+ * sums, per output sample and in a fixed order, the frames that cover it and
+ * its reflect images.  `saved` must come from a forward call with the same
+ * arguments.  Bit-reproducible; plain vector stores only.
+ *
+ * rave_stft_loss_workspace: bytes of `workspace` (pointers ignored), or -1 with
+ * the reason in rave_last_error.  All entry points validate before any launch
+ * (RAVE_ERR_ARG), allocate nothing, are asynchronous on the stream and
+ * graph-capturable. */
+#define RAVE_STFT_LOSS_V1 0
+#define RAVE_STFT_LOSS_MULTIRES 1
+int64_t rave_stft_loss_table_size(int n_fft, int win);
+int rave_stft_loss_pack_table(int n_fft, int win, float* out);
+
+typedef struct rave_stft_loss_args {
+    int32_t rows, t_len, n_res, kind;
+    int32_t n_fft[RAVE_STFT_MAX_SCALES];
+    int32_t hop[RAVE_STFT_MAX_SCALES];
+    int32_t win[RAVE_STFT_MAX_SCALES];
+    float log_epsilon;                            /* V1 only */
+    int32_t _pad0;
+    const float* tables[RAVE_STFT_MAX_SCALES];    /* per resolution, device */
+    const float* target;                          /* (rows, t_len) */
+    const float* value;                           /* (rows, t_len) */
+    float* workspace;
+    float* out;                                   /* 2 + 2 n_res floats */
+    float* saved;                                 /* 4 n_res floats: written by forward, read by backward */
+    const float* grad_out;                        /* backward: device, 2 floats (MULTIRES) or 1 (V1) */
+    float* grad_value;                            /* backward: (rows, t_len) */
+} rave_stft_loss_args;
+int64_t rave_stft_loss_workspace(const rave_stft_loss_args* a);
+int rave_stft_loss_forward(const rave_stft_loss_args* a, void* stream);
+int rave_stft_loss_backward(const rave_stft_loss_args* a, void* stream);
+
 /* ================================================================ pitch conditioning
  * The YIN estimator of rave/pitch_utils.py (estimate, _frame, _diff, _search
  * :15-86, bound by get_pitch :90-96) and the quantiser that turns an f0 contour

@@ -7,7 +7,7 @@ config / graph / weight utilities are importable without it.
 """
 from .config import RaveConfig, get_config  # noqa: F401
 
-__all__ = ["RaveConfig", "get_config", "RAVE", "AudioDistance", "MultiScaleSTFT",
+__all__ = ["RaveConfig", "get_config", "RAVE", "AudioDistance", "MultiScaleSTFT", "MultiResolutionSTFTLoss",
            "Yin", "F0OneHot", "PitchConditioner"]
 
 
@@ -18,7 +18,7 @@ def __getattr__(name):
     if name == "StreamingRAVE":
         from .streaming import StreamingRAVE
         return StreamingRAVE
-    if name in ("AudioDistance", "MultiScaleSTFT"):
+    if name in ("AudioDistance", "MultiScaleSTFT", "MultiResolutionSTFTLoss"):
         from . import distance
         return getattr(distance, name)
     if name in ("Yin", "F0OneHot", "PitchConditioner"):

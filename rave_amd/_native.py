@@ -211,6 +211,17 @@ class DistanceArgs(C.Structure):
                 ("workspace", vp), ("out", vp)]
 
 
+STFT_LOSS_V1, STFT_LOSS_MULTIRES = 0, 1       # RAVE_STFT_LOSS_*
+
+
+class StftLossArgs(C.Structure):
+    _fields_ = [("rows", i32), ("t_len", i32), ("n_res", i32), ("kind", i32),
+                ("n_fft", i32 * STFT_MAX_SCALES), ("hop", i32 * STFT_MAX_SCALES), ("win", i32 * STFT_MAX_SCALES),
+                ("log_epsilon", f32), ("_pad0", i32),
+                ("tables", vp * STFT_MAX_SCALES), ("target", vp), ("value", vp),
+                ("workspace", vp), ("out", vp), ("saved", vp), ("grad_out", vp), ("grad_value", vp)]
+
+
 class YinArgs(C.Structure):
     _fields_ = [("rows", i32), ("t_len", i32), ("sample_rate", i32), ("_pad0", i32),
                 ("pitch_min", C.c_double), ("pitch_max", C.c_double),
@@ -264,7 +275,7 @@ class Reloc(C.Structure):
 STRUCTS = [ConvArgs, AnalysisArgs, SynthesisArgs, FillArgs, RvqArgs, ShiftArgs, PlanOp, Reloc,
            CopyArgs, NoiseArgs, AdainArgs, UnitArgs, StackArgs, ModelConfig, Param, OpInfo,
            FirArgs, RowStatsArgs, AttnPoolArgs, LinearArgs, MaxPoolArgs, EdgeArgs,
-           StftArgs, DistanceArgs, YinArgs, F0OneHotArgs]
+           StftArgs, DistanceArgs, YinArgs, F0OneHotArgs, StftLossArgs]
 
 # every exported symbol of include/rave_amd.h
 EXPORTS = [
@@ -297,6 +308,8 @@ EXPORTS = [
     "rave_stft_table_size", "rave_stft_pack_table", "rave_stft_mag",
     "rave_audio_distance_workspace", "rave_audio_distance",
     "rave_yin_shape", "rave_yin", "rave_f0_onehot", "rave_pitch_onehot",
+    "rave_stft_loss_table_size", "rave_stft_loss_pack_table", "rave_stft_loss_workspace",
+    "rave_stft_loss_forward", "rave_stft_loss_backward",
 ]
 EDGE_FILTER_FLOATS = 8836   # RAVE_EDGE_FILTER_FLOATS
 
@@ -365,6 +378,13 @@ def _load():
     lib.rave_audio_distance_workspace.argtypes = [C.POINTER(DistanceArgs)]
     lib.rave_audio_distance_workspace.restype = i64
     lib.rave_audio_distance.argtypes = [C.POINTER(DistanceArgs), vp]
+    lib.rave_stft_loss_table_size.argtypes = [C.c_int, C.c_int]
+    lib.rave_stft_loss_table_size.restype = i64
+    lib.rave_stft_loss_pack_table.argtypes = [C.c_int, C.c_int, vp]
+    lib.rave_stft_loss_workspace.argtypes = [C.POINTER(StftLossArgs)]
+    lib.rave_stft_loss_workspace.restype = i64
+    lib.rave_stft_loss_forward.argtypes = [C.POINTER(StftLossArgs), vp]
+    lib.rave_stft_loss_backward.argtypes = [C.POINTER(StftLossArgs), vp]
     lib.rave_yin_shape.argtypes = [C.POINTER(YinArgs), C.POINTER(i32)]
     lib.rave_yin.argtypes = [C.POINTER(YinArgs), vp]
     lib.rave_f0_onehot.argtypes = [C.POINTER(F0OneHotArgs), vp]
@@ -581,6 +601,18 @@ def pack_stft_table(n: int):
         raise NotImplementedError(lib.rave_last_error().decode(errors="replace"))
     out = np.zeros(size, np.float32)
     check(lib.rave_stft_pack_table(int(n), out.ctypes.data), "stft_pack_table")
+    return out
+
+
+def pack_stft_loss_table(n_fft: int, win: int):
+    """Twiddle and window table of one loss resolution (rave_stft_loss_pack_table):
+    numpy float32, [(cos, -sin)(2 pi k / n_fft), k in [0, n_fft) | hann(win)]."""
+    import numpy as np
+    size = int(lib.rave_stft_loss_table_size(int(n_fft), int(win)))
+    if size <= 0:
+        raise ValueError(lib.rave_last_error().decode(errors="replace"))
+    out = np.zeros(size, np.float32)
+    check(lib.rave_stft_loss_pack_table(int(n_fft), int(win), out.ctypes.data), "stft_loss_pack_table")
     return out
 
 
