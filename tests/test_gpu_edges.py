@@ -150,6 +150,116 @@ def test_decoder_tail(N, dev, golden, causal, am, act, noise, F, B, prec):
         assert err <= 2e-6 * max(1.0, float(np.abs(ref).max())), err
 
 
+def _views():
+    from tests.test_gpu_aux_kernels import guarded, put, same_bits, untouched
+    return guarded, put, same_bits, untouched
+
+
+@pytest.mark.parametrize("prec", ["split16", "f32_ring", "bf16x3"])
+def test_encoder_head_on_guarded_views(N, dev, golden, prec):
+    """The head on views inside NaN-filled buffers: x_sb wider than the audio,
+    y_sc > frames and y_sb > 64 y_sc, once with rows the 16-byte stores can
+    take (y and both strides multiples of 4 floats) and once with rows they
+    cannot (the scalar stores); ragged F = 257, B = 2.  The file's bounds; the
+    guards still NaN and the input unchanged afterwards."""
+    from oracle.rave_oracle import conv1d, get_padding, reverse_half
+    guarded, put, same_bits, untouched = _views()
+    hkf, _ = _filters(golden)
+    F, B, nb, co, k, causal = 257, 2, 6, 64, 7, False
+    rng = np.random.default_rng(F)
+    T = 16 * F
+    x = (0.3 * np.sin(np.arange(T) * 0.05)[None] + 0.1 * rng.standard_normal((B, T))).astype(np.float32)
+    w = (rng.uniform(-1, 1, (co, nb, k)) / np.sqrt(nb * k)).astype(np.float32)
+    b = (0.1 * rng.standard_normal(co)).astype(np.float32)
+    ppad = get_padding(hkf.shape[-1], causal=causal)
+    bands = reverse_half(conv1d(x[:, None].astype(np.float64), hkf.astype(np.float64), None, stride=16, pad=ppad))[:, :nb]
+    cpad = get_padding(k, causal=causal)
+    ref = conv1d(bands, w.astype(np.float64), b.astype(np.float64), pad=cpad)
+    P = N.PRECISION[prec]
+    wprec = N.PREC_F32_RING if P == N.PREC_BF16X3 else P
+    packed = torch.from_numpy(N.pack_conv_weight(w, nb, co, k, 1, 1, 0, precision=wprec)).to(dev)
+    hd = torch.from_numpy(N.pack_edge_filter(hkf, head=True, n_out_bands=nb,
+                                             f32=P in (N.PREC_F32_RING, N.PREC_BF16X3))).to(dev)
+    bd = torch.from_numpy(b).to(dev)
+    xbuf, xd, _ = put(x, [(0, 1), (5, 3)])
+    x0 = xbuf.clone()
+    for ypads in ([(0, 1), (1, 2), (4, 3)], [(0, 1), (1, 2), (2, 3)]):      # y_sc = 264 (vector stores), 262 (scalar)
+        ybuf, y, ymask = guarded((B, co, F), ypads)
+        assert xd.stride(0) > T and y.stride(1) > F and y.stride(0) > co * y.stride(1)
+        a = N.EdgeArgs(batch=B, frames=F, conv_c_in=nb, conv_c_out=co, conv_kernel=k, conv_pad_left=cpad[0],
+                       pqmf_taps=hkf.shape[-1], pqmf_pad_left=ppad[0],
+                       x=xd.data_ptr(), x_sb=xd.stride(0), x_sc=xd.stride(0), y=y.data_ptr(), y_sb=y.stride(0),
+                       y_sc=y.stride(1), weight=packed.data_ptr(), bias=bd.data_ptr(), filter=hd.data_ptr(),
+                       precision=P)
+        N.check(N.lib.rave_encoder_head(C.byref(a), _st()), "encoder_head")
+        torch.cuda.synchronize()
+        got = y.cpu().numpy()
+        assert np.isfinite(got).all()
+        err = maxabs(got, ref)
+        assert err <= 2e-5 * float(np.abs(ref).max()), (ypads, err)
+        if prec == "bf16x3":
+            assert err <= 2e-6 * max(1.0, float(np.abs(ref).max())), (ypads, err)
+        assert untouched(ybuf, ymask) and same_bits(xbuf, x0)
+
+
+@pytest.mark.parametrize("prec", ["split16", "f32_ring", "bf16x3"])
+def test_decoder_tail_on_guarded_views(N, dev, golden, prec):
+    """The tail on views inside NaN-filled buffers: x_sc > frames with NaN rows
+    round the 64 channels, the noise likewise, y_sb > 16 frames (16-byte aligned,
+    as the launcher requires; the unaligned view is refused cleanly); ragged
+    F = 257, B = 2, amplitude modulation + noise, Snake."""
+    from oracle.rave_oracle import conv1d, get_padding, reverse_half, snake
+    guarded, put, same_bits, untouched = _views()
+    _, hki = _filters(golden)
+    F, B, ci, co, k, causal = 257, 2, 64, 32, 7, True
+    rng = np.random.default_rng(F + 1)
+    x = rng.standard_normal((B, ci, F)).astype(np.float32)
+    w = (rng.uniform(-1, 1, (co, ci, k)) / np.sqrt(ci * k)).astype(np.float32)
+    b = (0.1 * rng.standard_normal(co)).astype(np.float32)
+    alpha = (1 + 0.1 * rng.standard_normal(ci)).astype(np.float32)
+    nz = (0.05 * rng.standard_normal((B, 16, F))).astype(np.float32)
+    cpad = get_padding(k, causal=causal)
+    wv = conv1d(snake(x.astype(np.float64), alpha.reshape(-1, 1)), w.astype(np.float64), b.astype(np.float64), pad=cpad)
+    v, amp = np.split(wv, 2, axis=1)
+    wv = np.tanh(v * (1.0 / (1.0 + np.exp(-amp))) + nz)
+    spad = get_padding(hki.shape[-1], causal=causal)
+    ys = conv1d(reverse_half(wv), hki.astype(np.float64), None, pad=spad) * 16
+    ref = ys[:, ::-1, :].transpose(0, 2, 1).reshape(B, F * 16)
+    P = N.PRECISION[prec]
+    packed = torch.from_numpy(N.pack_conv_weight(w, ci, co, k, 1, 1, 0, precision=P)).to(dev)
+    hd = torch.from_numpy(N.pack_edge_filter(hki, head=False, f32=P in (N.PREC_F32_RING, N.PREC_BF16X3))).to(dev)
+    bd, ad = (torch.from_numpy(t).to(dev) for t in (b, alpha))
+    xbuf, xd, _ = put(x, [(0, 1), (1, 2), (3, 4)])
+    nbuf, nd, _ = put(nz, [(0, 1), (2, 1), (1, 6)])
+    x0, n0 = xbuf.clone(), nbuf.clone()
+
+    def call(ypads):
+        ybuf, y, ymask = guarded((B, 16 * F), ypads)
+        assert xd.stride(1) > F and nd.stride(1) > F and y.stride(0) > 16 * F
+        a = N.EdgeArgs(batch=B, frames=F, conv_c_in=ci, conv_c_out=co, conv_kernel=k, conv_pad_left=cpad[0],
+                       pqmf_taps=hki.shape[-1], pqmf_pad_left=spad[0], mode=1, act=N.ACT["snake"], leaky_slope=0.2,
+                       x=xd.data_ptr(), x_sb=xd.stride(0), x_sc=xd.stride(1), y=y.data_ptr(), y_sb=y.stride(0),
+                       weight=packed.data_ptr(), bias=bd.data_ptr(), alpha=ad.data_ptr(), filter=hd.data_ptr(),
+                       noise=nd.data_ptr(), n_sb=nd.stride(0), n_sc=nd.stride(1), precision=P)
+        rc = N.lib.rave_decoder_tail(C.byref(a), _st())
+        torch.cuda.synchronize()
+        assert untouched(ybuf, ymask) and same_bits(xbuf, x0) and same_bits(nbuf, n0)
+        return rc, ybuf, y
+
+    for ypads in ([(0, 1), (5, 7)], [(0, 1), (4, 9)]):                       # y off 16 bytes; y_sb % 4 != 0
+        rc, ybuf, _ = call(ypads)
+        assert rc == N.RAVE_ERR_ARG and "16-byte aligned" in N.lib.rave_last_error().decode()
+        assert bool(torch.isnan(ybuf).all())
+    rc, _, y = call([(0, 1), (4, 8)])
+    N.check(rc, "decoder_tail")
+    got = y.cpu().numpy()
+    assert np.isfinite(got).all()
+    err = maxabs(got, ref)
+    assert err <= 2e-5 * max(1.0, float(np.abs(ref).max())), err
+    if prec != "split16":
+        assert err <= 2e-6 * max(1.0, float(np.abs(ref).max())), err
+
+
 def test_edges_refuse_unsupported(N):
     a = N.EdgeArgs(batch=1, frames=64, conv_c_in=96, conv_c_out=32, conv_kernel=7, pqmf_taps=33, mode=1,
                    act=N.ACT["leaky"], x=16, y=16, weight=16, filter=16)
