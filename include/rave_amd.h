@@ -23,7 +23,11 @@
  *   rave_pqmf_synthesis  CachedPQMF.inverse rave/pqmf.py:275-284, optionally fused
  *                        with GeneratorV2's `x*sigmoid(a) (+noise) -> tanh`
  *                        epilogue rave/blocks.py:699-707.
- *   rave_fill_channels   the speaker-embedding concat of RAVE.encode
+ *   rave_pqmf_synthesis_backward / rave_pqmf_analysis_backward
+ *                        autograd's backward through those two, as the training
+ *                        step needs it between the decoder and the spectral loss
+ *                        (rave/model.py:358-391).
+ *   rave_fill_channels  the speaker-embedding concat of RAVE.encode
  *                        rave/model.py:618-620.
  *   rave_rvq_encode /    ResidualVectorQuantization.encode / decode
  *   rave_rvq_decode      rave/quantization.py:302-318.
@@ -235,6 +239,61 @@ typedef struct rave_pqmf_synthesis_args {
     int32_t _pad0;
 } rave_pqmf_synthesis_args;
 int rave_pqmf_synthesis(const rave_pqmf_synthesis_args* a, void* stream);
+
+/* ---------------------------------------------------------------- PQMF adjoints
+ * The backward passes of the two filterbank calls (pqmf_grad.hip; added under
+ * ABI 21, nothing existing changed).  Exact fp32 only: any precision but
+ * RAVE_PREC_F32 returns RAVE_ERR_ARG.  No atomics and no workspace: every
+ * output element is one gather written once, so two calls agree bit for bit.
+ *
+ * synthesis backward (CachedPQMF.inverse rave/pqmf.py:275-284 behind GeneratorV2's
+ * epilogue rave/blocks.py:699-707, as the loss meets them in rave/model.py:358-391):
+ * with v the epilogue's output (mode 0: v = x), the forward is linear in v and
+ *   gv[b, c, f] = n_band * rh(c, frame0 + f)
+ *                 * sum_{k, i} hki[n_band-1-i, c, k] * gy[b, (f - k + pad_left)*n_band + i]
+ * over the k with 0 <= f - k + pad_left < t_in, summed in (k, i) order.  The
+ * epilogue's derivative is recomputed from the saved inputs, s = sigmoid(x[n:2n]),
+ * t = tanh(.):
+ *   mode 0: gx = gv
+ *   mode 2: gx = gnoise = gv * (1 - t^2)                     t = tanh(x + noise)
+ *   mode 1: gnoise = gv * (1 - t^2)                          t = tanh(x[:n]*s + noise)
+ *           gx[:n] = gnoise * s,  gx[n:2n] = gnoise * x[:n] * s * (1 - s)
+ * gy: (B, t_in * n_band).  gx: (B, n_band or 2 n_band, x_len), every column
+ * f in [0, x_len) written (x_len = 0 means t_in; columns no output depends on
+ * get zeros).  gnoise: (B, n_band, x_len), written when not NULL.  x may be
+ * NULL in mode 0, noise may be NULL in every mode (it reads as zero).
+ * pad_left, frame0, x_len, t_in: the forward call's.
+ */
+typedef struct rave_pqmf_synthesis_backward_args {
+    int32_t n_band, taps, batch, t_in;
+    int32_t pad_left, mode, frame0, x_len;
+    const float* gy;    int64_t gy_sb;
+    const float* x;     int64_t x_sb, x_sc;
+    const float* noise; int64_t n_sb, n_sc;
+    float* gx;          int64_t gx_sb, gx_sc;
+    float* gnoise;      int64_t gn_sb, gn_sc;
+    const float* hki;   /* (n_band, n_band, taps) */
+    int32_t precision;  /* RAVE_PREC_F32 */
+    int32_t _pad0;
+} rave_pqmf_synthesis_backward_args;
+int rave_pqmf_synthesis_backward(const rave_pqmf_synthesis_backward_args* a, void* stream);
+
+/* analysis backward (CachedPQMF.forward rave/pqmf.py:269-273 + reverse_half :13-17):
+ *   gx[b, s] = sum_{band < n_out_bands} sum_t rh(band, t) * hkf[band, s + pad_left - t*n_band] * gy[b, band, t]
+ * over 0 <= t < t_out and 0 <= s + pad_left - t*n_band < taps; with s = n_band*u + i
+ * and d = u + pad_left/n_band - t the sum runs in (d, band) order.  Every
+ * s in [0, t_in) is written.  pad_left must be a multiple of n_band (256, 512
+ * and 0 in every use); nothing may be NULL.  gy: (B, n_out_bands, t_out).
+ */
+typedef struct rave_pqmf_analysis_backward_args {
+    int32_t n_band, taps, n_out_bands, batch;
+    int32_t t_in, pad_left;
+    int32_t t_out, precision;   /* RAVE_PREC_F32 */
+    const float* gy; int64_t gy_sb, gy_sc;
+    float* gx;       int64_t gx_sb;
+    const float* hkf;
+} rave_pqmf_analysis_backward_args;
+int rave_pqmf_analysis_backward(const rave_pqmf_analysis_backward_args* a, void* stream);
 
 /* ---------------------------------------------------------------- misc */
 /* y[b, c, t] = values[b * values_sb + c] for c < channels, t < t_len (speaker

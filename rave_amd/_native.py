@@ -91,6 +91,25 @@ class SynthesisArgs(C.Structure):
                 ("hki", vp), ("precision", i32), ("_pad0", i32)]
 
 
+class SynthesisBackwardArgs(C.Structure):
+    _fields_ = [("n_band", i32), ("taps", i32), ("batch", i32), ("t_in", i32),
+                ("pad_left", i32), ("mode", i32), ("frame0", i32), ("x_len", i32),
+                ("gy", vp), ("gy_sb", i64),
+                ("x", vp), ("x_sb", i64), ("x_sc", i64),
+                ("noise", vp), ("n_sb", i64), ("n_sc", i64),
+                ("gx", vp), ("gx_sb", i64), ("gx_sc", i64),
+                ("gnoise", vp), ("gn_sb", i64), ("gn_sc", i64),
+                ("hki", vp), ("precision", i32), ("_pad0", i32)]
+
+
+class AnalysisBackwardArgs(C.Structure):
+    _fields_ = [("n_band", i32), ("taps", i32), ("n_out_bands", i32), ("batch", i32),
+                ("t_in", i32), ("pad_left", i32), ("t_out", i32), ("precision", i32),
+                ("gy", vp), ("gy_sb", i64), ("gy_sc", i64),
+                ("gx", vp), ("gx_sb", i64),
+                ("hkf", vp)]
+
+
 class FillArgs(C.Structure):
     # values_sb: row stride of `values` (0: one vector broadcast to every batch row)
     _fields_ = [("batch", i32), ("channels", i32), ("t_len", i32), ("values_sb", i32),
@@ -275,7 +294,8 @@ class Reloc(C.Structure):
 STRUCTS = [ConvArgs, AnalysisArgs, SynthesisArgs, FillArgs, RvqArgs, ShiftArgs, PlanOp, Reloc,
            CopyArgs, NoiseArgs, AdainArgs, UnitArgs, StackArgs, ModelConfig, Param, OpInfo,
            FirArgs, RowStatsArgs, AttnPoolArgs, LinearArgs, MaxPoolArgs, EdgeArgs,
-           StftArgs, DistanceArgs, YinArgs, F0OneHotArgs, StftLossArgs]
+           StftArgs, DistanceArgs, YinArgs, F0OneHotArgs, SynthesisBackwardArgs, AnalysisBackwardArgs,
+           StftLossArgs]
 
 # every exported symbol of include/rave_amd.h
 EXPORTS = [
@@ -283,7 +303,8 @@ EXPORTS = [
     "rave_conv1d_chunk", "rave_conv1d_packed_size", "rave_conv1d_pack_weight", "rave_conv1d",
     "rave_conv1d_workspace", "rave_conv1d_configs", "rave_conv1d_split_packed_size", "rave_conv1d_split_pack_weight",
     "rave_conv1d_ring_pack_weight", "rave_conv1d_bf3_packed_size", "rave_conv1d_bf3_pack_weight",
-    "rave_pqmf_analysis", "rave_pqmf_synthesis", "rave_fill_channels", "rave_copy",
+    "rave_pqmf_analysis", "rave_pqmf_synthesis", "rave_pqmf_analysis_backward", "rave_pqmf_synthesis_backward",
+    "rave_fill_channels", "rave_copy",
     "rave_rvq_workspace", "rave_rvq_encode", "rave_rvq_decode", "rave_shift_history", "rave_noise_synth", "rave_adain",
     "rave_unit_packed_size", "rave_unit_pack_weight", "rave_residual_unit",
     "rave_unit_split_packed_size", "rave_unit_split_pack_weight", "rave_unit_ring_pack_weight",
@@ -363,6 +384,8 @@ def _load():
     lib.rave_rvq_workspace.restype = i64
     for name, st in [("rave_conv1d", ConvArgs), ("rave_pqmf_analysis", AnalysisArgs),
                      ("rave_pqmf_synthesis", SynthesisArgs), ("rave_fill_channels", FillArgs),
+                     ("rave_pqmf_synthesis_backward", SynthesisBackwardArgs),
+                     ("rave_pqmf_analysis_backward", AnalysisBackwardArgs),
                      ("rave_rvq_encode", RvqArgs), ("rave_rvq_decode", RvqArgs),
                      ("rave_shift_history", ShiftArgs), ("rave_copy", CopyArgs),
                      ("rave_noise_synth", NoiseArgs), ("rave_adain", AdainArgs),

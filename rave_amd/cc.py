@@ -259,7 +259,15 @@ class CachedPQMF(nn.Module):
     (k 513, stride n_band, padding get_padding(513)) + reverse_half (optionally
     only the first ``n_out`` bands, RAVE.encode's x[:, :6], rave/model.py:613);
     ``inverse`` = reverse_half + polyphase synthesis (k 33) * n_band + band
-    flip + interleave.  Cached mode keeps taps-1 audio samples / frames."""
+    flip + interleave.  Cached mode keeps taps-1 audio samples / frames.
+
+    Not cached, both are differentiable (exact fp32 only): the ops carry an
+    autograd implementation over the adjoint kernels (rave_pqmf_*_backward), so
+    ``forward(x)`` and ``inverse(x, mode, noise)`` return a ``grad_fn`` when x
+    (or noise) requires grad, epilogue modes 1 and 2 included; the filters are
+    constants and get no gradient, and there is no double backward.  The cached
+    (streaming) mode is as it was: its history buffers are state, not a
+    function of the call's input, and its results carry no ``grad_fn``."""
 
     def __init__(self, attenuation: float = 100.0, n_band: int = 16, hk=None):
         super().__init__()

@@ -8,6 +8,7 @@
 //
 // Only tensors, ints and strings cross this file; every launch goes through
 // the C-ABI (include/rave_amd.h rave_model_* / rave_stream_*).
+#include <torch/csrc/autograd/custom_function.h>
 #include <torch/custom_class.h>
 #include <torch/script.h>
 
@@ -450,6 +451,153 @@ at::Tensor pqmf_synthesis_op(at::Tensor x, at::Tensor hki, int64_t pad_left, int
     return y;
 }
 
+// rave_amd::pqmf_analysis_backward -- the adjoint of pqmf_analysis on
+// rave_pqmf_analysis_backward: gy (B, n_out_bands, t_out) -> gx (B, 1, t_in)
+at::Tensor pqmf_analysis_backward_op(at::Tensor gy, at::Tensor hkf, int64_t n_out_bands, int64_t pad_left,
+                                     int64_t t_in) {
+    seam_tensor(gy, "gy");
+    c10::hip::HIPGuard g((c10::DeviceIndex)gy.get_device());
+    TORCH_CHECK_VALUE(gy.size(1) == n_out_bands, "gy must be (B, n_out_bands, t_out)");
+    at::Tensor h = hkf.to(gy.device(), at::kFloat).contiguous();
+    const int64_t B = gy.size(0);
+    at::Tensor gx = at::empty({B, 1, t_in}, gy.options());
+    rave_pqmf_analysis_backward_args a{};
+    a.n_band = (int)h.size(0); a.taps = (int)h.size(1); a.n_out_bands = (int)n_out_bands; a.batch = (int)B;
+    a.t_in = (int)t_in; a.pad_left = (int)pad_left; a.t_out = (int)gy.size(2); a.precision = RAVE_PREC_F32;
+    a.gy = gy.data_ptr<float>(); a.gy_sb = gy.stride(0); a.gy_sc = gy.stride(1);
+    a.gx = gx.data_ptr<float>(); a.gx_sb = gx.stride(0);
+    a.hkf = h.data_ptr<float>();
+    check(rave_pqmf_analysis_backward(&a, cur_stream(gy)), "pqmf_analysis_backward");
+    return gx;
+}
+
+// rave_amd::pqmf_synthesis_backward -- the adjoint of pqmf_synthesis with the
+// epilogue's derivative (rave_pqmf_synthesis_backward): gy (B, 1, F n_band) and
+// the forward call's x / noise -> gx like x, gnoise like noise (None without)
+std::tuple<at::Tensor, c10::optional<at::Tensor>> pqmf_synthesis_backward_op(
+    at::Tensor gy, at::Tensor x, at::Tensor hki, int64_t pad_left, int64_t frames, int64_t frame0, int64_t x_len,
+    int64_t mode, c10::optional<at::Tensor> noise) {
+    seam_tensor(gy, "gy");
+    seam_tensor(x, "x");
+    c10::hip::HIPGuard g((c10::DeviceIndex)x.get_device());
+    at::Tensor h = hki.to(x.device(), at::kFloat).contiguous();
+    const int64_t nb = h.size(0), B = x.size(0), XL = x.size(2);
+    TORCH_CHECK_VALUE(mode >= 0 && mode <= 2, "mode must be 0 (plain), 1 (amplitude modulation) or 2 (tanh)");
+    TORCH_CHECK_VALUE(x.size(1) == (mode == 1 ? 2 * nb : nb), "x must have ", mode == 1 ? 2 * nb : nb, " channels");
+    TORCH_CHECK_VALUE(mode != 0 || !noise.has_value(), "noise needs an epilogue mode");
+    TORCH_CHECK_VALUE(x_len == XL, "x_len must be x's length");
+    const int64_t F = frames > 0 ? frames : XL;
+    TORCH_CHECK_VALUE(gy.size(0) == B && gy.size(1) == 1 && gy.size(2) == F * nb, "gy must be (B, 1, frames n_band)");
+    at::Tensor gx = at::empty({B, x.size(1), XL}, x.options());
+    rave_pqmf_synthesis_backward_args a{};
+    a.n_band = (int)nb; a.taps = (int)h.size(2); a.batch = (int)B; a.t_in = (int)F; a.pad_left = (int)pad_left;
+    a.mode = (int)mode; a.frame0 = (int)frame0; a.x_len = (int)XL;
+    a.gy = gy.data_ptr<float>(); a.gy_sb = gy.stride(0);
+    a.x = x.data_ptr<float>(); a.x_sb = x.stride(0); a.x_sc = x.stride(1);
+    a.gx = gx.data_ptr<float>(); a.gx_sb = gx.stride(0); a.gx_sc = gx.stride(1);
+    c10::optional<at::Tensor> gnoise;
+    at::Tensor nz, gn;
+    if (noise.has_value()) {
+        nz = *noise;
+        seam_tensor(nz, "noise");
+        TORCH_CHECK_VALUE(nz.size(0) == B && nz.size(1) == nb && nz.size(2) == XL,
+                          "noise must be (B, n_band, x_len), time contiguous");
+        gn = at::empty({B, nb, XL}, x.options());
+        a.noise = nz.data_ptr<float>(); a.n_sb = nz.stride(0); a.n_sc = nz.stride(1);
+        a.gnoise = gn.data_ptr<float>(); a.gn_sb = gn.stride(0); a.gn_sc = gn.stride(1);
+        gnoise = gn;
+    }
+    a.hki = h.data_ptr<float>(); a.precision = RAVE_PREC_F32;
+    check(rave_pqmf_synthesis_backward(&a, cur_stream(x)), "pqmf_synthesis_backward");
+    return std::make_tuple(gx, gnoise);
+}
+
+// Autograd for the two PQMF ops (registered on the autograd key below, so
+// scripted modules and TorchScript hosts get it too): the forward is the op
+// itself; the backward is one adjoint call.  The filters are constants (no
+// gradient); exact fp32 only; no double backward.
+void no_double_backward(const char* op) {
+    TORCH_CHECK_NOT_IMPLEMENTED(!at::GradMode::is_enabled(), op, ": double backward is not implemented");
+}
+
+struct PqmfAnalysisFn : torch::autograd::Function<PqmfAnalysisFn> {
+    static at::Tensor forward(torch::autograd::AutogradContext* ctx, at::Tensor x, at::Tensor hkf, int64_t n_out_bands,
+                              int64_t pad_left, int64_t precision) {
+        at::AutoDispatchBelowADInplaceOrView below;
+        ctx->save_for_backward({hkf});
+        ctx->saved_data["n_out_bands"] = n_out_bands;
+        ctx->saved_data["pad_left"] = pad_left;
+        ctx->saved_data["t_in"] = x.size(2);
+        return pqmf_analysis_op(x, hkf, n_out_bands, pad_left, precision);
+    }
+    static torch::autograd::variable_list backward(torch::autograd::AutogradContext* ctx,
+                                                   torch::autograd::variable_list grads) {
+        no_double_backward("pqmf_analysis");
+        at::AutoDispatchBelowADInplaceOrView below;
+        const auto saved = ctx->get_saved_variables();
+        at::Tensor gx = pqmf_analysis_backward_op(grads[0].contiguous(), saved[0], ctx->saved_data["n_out_bands"].toInt(),
+                                                  ctx->saved_data["pad_left"].toInt(), ctx->saved_data["t_in"].toInt());
+        return {gx, at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor()};
+    }
+};
+
+struct PqmfSynthesisFn : torch::autograd::Function<PqmfSynthesisFn> {
+    static at::Tensor forward(torch::autograd::AutogradContext* ctx, at::Tensor x, at::Tensor hki, int64_t pad_left,
+                              int64_t frames, int64_t frame0, int64_t precision, int64_t mode,
+                              c10::optional<at::Tensor> noise) {
+        at::AutoDispatchBelowADInplaceOrView below;
+        ctx->save_for_backward({x, hki, noise.has_value() ? *noise : at::Tensor()});
+        ctx->saved_data["pad_left"] = pad_left;
+        ctx->saved_data["frames"] = frames;
+        ctx->saved_data["frame0"] = frame0;
+        ctx->saved_data["mode"] = mode;
+        return pqmf_synthesis_op(x, hki, pad_left, frames, frame0, precision, mode, noise);
+    }
+    static torch::autograd::variable_list backward(torch::autograd::AutogradContext* ctx,
+                                                   torch::autograd::variable_list grads) {
+        no_double_backward("pqmf_synthesis");
+        at::AutoDispatchBelowADInplaceOrView below;
+        const auto saved = ctx->get_saved_variables();
+        c10::optional<at::Tensor> noise;
+        if (saved[2].defined()) noise = saved[2];
+        auto g = pqmf_synthesis_backward_op(grads[0].contiguous(), saved[0], saved[1],
+                                            ctx->saved_data["pad_left"].toInt(), ctx->saved_data["frames"].toInt(),
+                                            ctx->saved_data["frame0"].toInt(), saved[0].size(2),
+                                            ctx->saved_data["mode"].toInt(), noise);
+        at::Tensor gn = std::get<1>(g).has_value() ? *std::get<1>(g) : at::Tensor();
+        return {std::get<0>(g), at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor(), at::Tensor(), gn};
+    }
+};
+
+bool wants_grad(const at::Tensor& x, const c10::optional<at::Tensor>& other, int64_t precision, const char* op) {
+    if (!at::GradMode::is_enabled() || !(x.requires_grad() || (other.has_value() && other->requires_grad())))
+        return false;
+    TORCH_CHECK_NOT_IMPLEMENTED(precision == RAVE_PREC_F32, op,
+                                ": only the exact fp32 precision (0) is differentiable; got precision ", precision,
+                                " with an input that requires grad");
+    return true;
+}
+
+at::Tensor pqmf_analysis_autograd(at::Tensor x, at::Tensor hkf, int64_t n_out_bands, int64_t pad_left,
+                                  int64_t precision) {
+    if (wants_grad(x, c10::nullopt, precision, "pqmf_analysis")) {
+        seam_tensor(x, "x");
+        return PqmfAnalysisFn::apply(x, hkf, n_out_bands, pad_left, precision);
+    }
+    at::AutoDispatchBelowADInplaceOrView below;
+    return pqmf_analysis_op(x, hkf, n_out_bands, pad_left, precision);
+}
+
+at::Tensor pqmf_synthesis_autograd(at::Tensor x, at::Tensor hki, int64_t pad_left, int64_t frames, int64_t frame0,
+                                   int64_t precision, int64_t mode, c10::optional<at::Tensor> noise) {
+    if (wants_grad(x, noise, precision, "pqmf_synthesis")) {
+        seam_tensor(x, "x");
+        return PqmfSynthesisFn::apply(x, hki, pad_left, frames, frame0, precision, mode, noise);
+    }
+    at::AutoDispatchBelowADInplaceOrView below;
+    return pqmf_synthesis_op(x, hki, pad_left, frames, frame0, precision, mode, noise);
+}
+
 // rave_amd::adain -- AdaptiveInstanceNormalization.forward in eval mode
 // (rave/blocks.py:856-919) on rave_adain over the module's own buffers
 // (mean_x / std_x / mean_y / std_y (max_batch, C, 1), num_update_x / _y (1,)):
@@ -605,6 +753,11 @@ TORCH_LIBRARY(rave_amd, lib) {
     lib.def("pqmf_synthesis(Tensor x, Tensor hki, int pad_left, int frames, int frame0, int precision, int mode=0, "
             "Tensor? noise=None) -> Tensor",
             &pqmf_synthesis_op);
+    lib.def("pqmf_analysis_backward(Tensor gy, Tensor hkf, int n_out_bands, int pad_left, int t_in) -> Tensor",
+            &pqmf_analysis_backward_op);
+    lib.def("pqmf_synthesis_backward(Tensor gy, Tensor x, Tensor hki, int pad_left, int frames, int frame0, "
+            "int x_len, int mode, Tensor? noise=None) -> (Tensor gx, Tensor? gnoise)",
+            &pqmf_synthesis_backward_op);
     lib.def("adain(Tensor x, Tensor(a!) mean_x, Tensor(b!) std_x, Tensor(c!) mean_y, Tensor(d!) std_y, "
             "Tensor(e!) num_update_x, Tensor(f!) num_update_y, int mode) -> Tensor",
             &adain_op);
@@ -643,4 +796,11 @@ TORCH_LIBRARY(rave_amd, lib) {
                 return c10::make_intrusive<Engine>(std::get<0>(st), std::get<1>(st), std::get<2>(st), std::get<3>(st),
                                                    std::get<4>(st), std::get<5>(st), std::get<6>(st));
             });
+}
+
+// A direct registration on the GPU's autograd key: the ops above are defined
+// with catch-all kernels, which the dispatcher would otherwise also use there.
+TORCH_LIBRARY_IMPL(rave_amd, AutogradCUDA, m) {
+    m.impl("pqmf_analysis", &pqmf_analysis_autograd);
+    m.impl("pqmf_synthesis", &pqmf_synthesis_autograd);
 }
