@@ -295,6 +295,60 @@ typedef struct rave_pqmf_analysis_backward_args {
 } rave_pqmf_analysis_backward_args;
 int rave_pqmf_analysis_backward(const rave_pqmf_analysis_backward_args* a, void* stream);
 
+/* ---------------------------------------------------------------- conv1d backward
+ * The backward of the non-transposed rave_conv1d (conv_grad.hip; added under ABI
+ * 21, nothing existing changed): autograd through cc.Conv1d, its fused input
+ * activation, bias and residual.  Exact fp32 only, offline (non-cached) calls.
+ * With a = act(x), zero outside [0, t_in), s = stride, d = dilation, pl = pad_left:
+ *   gbias[m]     = sum_{b, n} gy[b, m, n]
+ *   gweight[m, ci, j] = sum_{b, n} gy[b, m, n] * a[b, ci, n*s + j*d - pl]
+ *   ga[b, ci, t] = sum_{m, j} W[m, ci, j] * gy[b, m, (t + pl - j*d)/s]
+ *                  over the j with s | (t + pl - j*d) and 0 <= n < t_out
+ *   gx           = ga * act'(x)
+ *   galpha[ci]   = sum_{b, t} ga[b, ci, t] * d act / d alpha (x[b, ci, t])     (Snake)
+ * act' of LeakyReLU is slope at x <= 0; of Snake 1 + alpha sin(2 alpha x)/(alpha + 1e-9);
+ * d act / d alpha = x sin(2 alpha x)/(alpha + 1e-9) - sin(alpha x)^2/(alpha + 1e-9)^2.
+ * The residual's gradient is gy itself and needs no call.  Input columns no
+ * output reads (a right tail the stride leaves) get zeros in gx.
+ *
+ * weight and gweight are in torch layout (c_out, c_in, kernel), read from and
+ * written to device memory as they are: no packed image on this path.  x, gy
+ * and gx have free batch and channel strides and stride-1 time.  Any of gx /
+ * gweight / gbias / galpha may be NULL, which skips it; x may be NULL when
+ * neither an activation nor gweight needs it.  rave_conv1d_backward_data writes
+ * gx and galpha, rave_conv1d_backward_weight gweight and gbias; both take the
+ * same struct.  workspace: rave_conv1d_backward_workspace() floats for these args
+ * (output pointers set): the weight gradient's split-K slabs (0 when it runs
+ * unsplit) plus, when galpha is asked of a Snake conv, one row of c_in partials
+ * per data-kernel workgroup column.  Nothing in it needs zeroing.  No atomics:
+ * slabs and partials are summed in a fixed order, two calls agree bit for bit.
+ * A shape rave_conv1d refuses gets the same status here; transposed = 1 and
+ * any precision but RAVE_PREC_F32 return RAVE_ERR_ARG.
+ */
+typedef struct rave_conv1d_backward_args {
+    int32_t c_in, c_out, kernel, stride, dilation;
+    int32_t pad_left, pad_right;
+    int32_t transposed;     /* must be 0                                         */
+    int32_t out_shift;      /* unused                                            */
+    int32_t act;            /* RAVE_ACT_*                                        */
+    float   leaky_slope;
+    int32_t batch, t_in, t_out;
+    int32_t precision;      /* RAVE_PREC_F32                                     */
+    int32_t _pad0;
+    const float* x;       int64_t x_sb, x_sc;     /* the forward's input         */
+    const float* gy;      int64_t gy_sb, gy_sc;   /* (B, c_out, t_out)           */
+    float* gx;            int64_t gx_sb, gx_sc;   /* (B, c_in, t_in) or NULL     */
+    const float* weight;  /* (c_out, c_in, kernel), torch layout                 */
+    const float* alpha;   /* c_in Snake alphas (act == RAVE_ACT_SNAKE)           */
+    float* gweight;       /* (c_out, c_in, kernel) or NULL                       */
+    float* gbias;         /* c_out or NULL                                       */
+    float* galpha;        /* c_in or NULL (Snake only)                           */
+    float* workspace;     /* rave_conv1d_backward_workspace() floats, or NULL when 0 */
+} rave_conv1d_backward_args;
+int64_t rave_conv1d_backward_workspace(const rave_conv1d_backward_args* a);
+int rave_conv1d_backward_data(const rave_conv1d_backward_args* a, void* stream);
+int rave_conv1d_backward_weight(const rave_conv1d_backward_args* a, void* stream);
+
 /* ---------------------------------------------------------------- misc */
 /* y[b, c, t] = values[b * values_sb + c] for c < channels, t < t_len (speaker
  * concat).  values_sb: row stride of `values` in floats; 0 (a zero-initialised

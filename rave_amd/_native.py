@@ -110,6 +110,18 @@ class AnalysisBackwardArgs(C.Structure):
                 ("hkf", vp)]
 
 
+class ConvBackwardArgs(C.Structure):
+    _fields_ = [("c_in", i32), ("c_out", i32), ("kernel", i32), ("stride", i32), ("dilation", i32),
+                ("pad_left", i32), ("pad_right", i32), ("transposed", i32), ("out_shift", i32),
+                ("act", i32), ("leaky_slope", C.c_float), ("batch", i32), ("t_in", i32), ("t_out", i32),
+                ("precision", i32), ("_pad0", i32),
+                ("x", vp), ("x_sb", i64), ("x_sc", i64),
+                ("gy", vp), ("gy_sb", i64), ("gy_sc", i64),
+                ("gx", vp), ("gx_sb", i64), ("gx_sc", i64),
+                ("weight", vp), ("alpha", vp),
+                ("gweight", vp), ("gbias", vp), ("galpha", vp), ("workspace", vp)]
+
+
 class FillArgs(C.Structure):
     # values_sb: row stride of `values` (0: one vector broadcast to every batch row)
     _fields_ = [("batch", i32), ("channels", i32), ("t_len", i32), ("values_sb", i32),
@@ -295,13 +307,14 @@ STRUCTS = [ConvArgs, AnalysisArgs, SynthesisArgs, FillArgs, RvqArgs, ShiftArgs, 
            CopyArgs, NoiseArgs, AdainArgs, UnitArgs, StackArgs, ModelConfig, Param, OpInfo,
            FirArgs, RowStatsArgs, AttnPoolArgs, LinearArgs, MaxPoolArgs, EdgeArgs,
            StftArgs, DistanceArgs, YinArgs, F0OneHotArgs, SynthesisBackwardArgs, AnalysisBackwardArgs,
-           StftLossArgs]
+           ConvBackwardArgs, StftLossArgs]
 
 # every exported symbol of include/rave_amd.h
 EXPORTS = [
     "rave_last_error", "rave_abi_version", "rave_struct_sizes",
     "rave_conv1d_chunk", "rave_conv1d_packed_size", "rave_conv1d_pack_weight", "rave_conv1d",
-    "rave_conv1d_workspace", "rave_conv1d_configs", "rave_conv1d_split_packed_size", "rave_conv1d_split_pack_weight",
+    "rave_conv1d_workspace", "rave_conv1d_backward_workspace", "rave_conv1d_backward_data",
+    "rave_conv1d_backward_weight", "rave_conv1d_configs", "rave_conv1d_split_packed_size", "rave_conv1d_split_pack_weight",
     "rave_conv1d_ring_pack_weight", "rave_conv1d_bf3_packed_size", "rave_conv1d_bf3_pack_weight",
     "rave_pqmf_analysis", "rave_pqmf_synthesis", "rave_pqmf_analysis_backward", "rave_pqmf_synthesis_backward",
     "rave_fill_channels", "rave_copy",
@@ -380,12 +393,16 @@ def _load():
     lib.rave_unit_bf3_packed_size.restype = i64
     lib.rave_unit_bf3_pack_weight.argtypes = [vp, vp, C.c_int, vp]
     lib.rave_conv1d_workspace.restype = i64
+    lib.rave_conv1d_backward_workspace.argtypes = [C.POINTER(ConvBackwardArgs)]
+    lib.rave_conv1d_backward_workspace.restype = i64
     lib.rave_rvq_workspace.argtypes = [C.POINTER(RvqArgs)]
     lib.rave_rvq_workspace.restype = i64
     for name, st in [("rave_conv1d", ConvArgs), ("rave_pqmf_analysis", AnalysisArgs),
                      ("rave_pqmf_synthesis", SynthesisArgs), ("rave_fill_channels", FillArgs),
                      ("rave_pqmf_synthesis_backward", SynthesisBackwardArgs),
                      ("rave_pqmf_analysis_backward", AnalysisBackwardArgs),
+                     ("rave_conv1d_backward_data", ConvBackwardArgs),
+                     ("rave_conv1d_backward_weight", ConvBackwardArgs),
                      ("rave_rvq_encode", RvqArgs), ("rave_rvq_decode", RvqArgs),
                      ("rave_shift_history", ShiftArgs), ("rave_copy", CopyArgs),
                      ("rave_noise_synth", NoiseArgs), ("rave_adain", AdainArgs),

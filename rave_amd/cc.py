@@ -150,7 +150,14 @@ class Conv1d(_PackedConv):
     ``slope`` or ACT_SNAKE with ``alpha``) and residual (``forward(x, res)``).
     ``forward(x, res, act, slope, alpha)`` with ``act >= 0`` takes the input
     activation of this call instead (the module tree fuses the activation
-    module in front of each conv this way: rave_amd.modules)."""
+    module in front of each conv this way: rave_amd.modules).
+
+    In exact fp32, offline and eager, the call is differentiable: it goes
+    through ``rave_amd::conv1d_w`` (the same kernel launch, same bits), whose
+    autograd implementation returns the gradients of x, ``weight``, ``bias``,
+    a Snake ``alpha`` and the residual from the conv_grad kernels.  split16,
+    cached and scripted modules call ``rave_amd::conv1d`` as before and carry
+    no ``grad_fn``; there is no double backward."""
 
     def __init__(self, in_channels: int, out_channels: int, kernel_size: int, stride: int = 1, padding=0,
                  dilation: int = 1, groups: int = 1, bias: bool = True, cumulative_delay: int = 0,
@@ -184,6 +191,11 @@ class Conv1d(_PackedConv):
             pl, pr = 0, 0
         else:
             pl, pr = self.pad_l, self.pad_r
+            if self.precision == 0 and not torch.jit.is_scripting():
+                # exact fp32, offline, eager: the same launch with an autograd edge to weight / bias / alpha
+                return torch.ops.rave_amd.conv1d_w(x.contiguous(), self.weight, packed, self.bias, alpha, residual,
+                                                   self.c_out, self.kernel, self.stride, self.dilation, pl, pr, act,
+                                                   slope, self.precision)
         return torch.ops.rave_amd.conv1d(x.contiguous(), packed, self.bias, alpha, residual, self.c_out, self.kernel,
                                          self.stride, self.dilation, pl, pr, False, 0, act, slope, self.precision)
 

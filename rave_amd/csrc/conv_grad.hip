@@ -1,0 +1,465 @@
+// Backward of the non-transposed rave_conv1d (gfx950), exact fp32 only: the data
+// gradient, the weight / bias gradient and Snake's alpha gradient.
+//
+// With a = act(x), zero outside [0, t_in), and the forward
+//   y[b, m, n] = bias[m] + sum_{ci, j} W[m, ci, j] a[b, ci, n s + j d - pl]  (+ res[b, m, n])
+// the kernels here compute
+//   ga[b, ci, t] = sum_{j, m} W[m, ci, j] gy[b, m, (t + pl - j d) / s]     gx = ga act'(x)
+//   gW[m, ci, j] = sum_{b, n} gy[b, m, n] a[b, ci, n s + j d - pl]          gbias[m] = sum_{b, n} gy[b, m, n]
+//   galpha[ci]   = sum_{b, t} ga[b, ci, t] d act / d alpha (x[b, ci, t])
+// on v_mfma_f32_16x16x4_f32 (a k-ordered fmaf chain per output element).
+//
+// data:   rows ci, columns u of one output phase p (t = s u + p), K = (i, m): phase p
+//         sees the k / s taps j = j0 + s i, j0 = (p + pl) mod s, at
+//         n = u + (p + pl) / s - i d, a stride-1 gather.  The s phases are s
+//         sub-problems (grid z = batch x phase): no column is computed and dropped.
+// weight: rows m, columns (j, ci) in blocks of 16 ci per tap, K = (b, n); the grid's
+//         z splits K into slabs, summed in slab order by a second launch.
+// Both operands sit in LDS as [channel][time] rows whose strides make every
+// fragment read (ds_read_b32: banks mod 32 per 32-lane half) conflict-free:
+// the operand whose 16 lanes walk time needs a row stride of 16 mod 32 (the
+// other half's two k rows then land on the other 16 banks); the operand whose
+// 16 lanes walk channels needs a row stride of 2 x odd (banks 2 row' + k).
+//
+// No atomics; nothing in the workspace needs zeroing; every output element is
+// written once by a plain vector-memory store; two calls agree bit for bit.
+#include "conv_shared.h"
+
+namespace rave {
+
+struct CgArgs {
+    const float* x; const float* gy; const float* w; const float* alpha;
+    float* gx; float* gw; float* gb; float* galpha;
+    float* slabs;                 // weight split-K slabs (S > 1)
+    float* apart;                 // alpha partials, (workgroups of the data grid per ci tile) x c_in
+    int64_t x_sb, x_sc, gy_sb, gy_sc, gx_sb, gx_sc;
+    int c_in, c_out, k, s, d, pl, t_in, t_out, B, act;
+    float slope;
+    int S, cps, nch, tch;         // weight: K splits, chunks per split, chunks, chunks per batch item
+    int P;                        // alpha partial rows
+};
+
+// sin(2 z) and sin(z)^2 on sin_squared's reduction and polynomials (common.h):
+// z = r + q pi/2, so sin(2 z) = (-1)^q 2 sin r cos r and sin(z)^2 = q odd ? cos(r)^2 : sin(r)^2.
+__device__ __forceinline__ void snake_parts(float z, float& sin2, float& ssq) {
+    const float q = rintf(z * 0.636619772367581343f);
+    float r = fmaf(q, -1.57079637050628662109375f, z);
+    r = fmaf(q, 4.371138828673793e-08f, r);
+    r = fmaf(q, 1.7151245100058819e-15f, r);
+    const float zz = r * r;
+    const float s = fmaf(fmaf(fmaf(-1.9515295891e-4f, zz, 8.3321608736e-3f), zz, -1.6666654611e-1f), zz * r, r);
+    const float c = fmaf(fmaf(fmaf(2.443315711809948e-5f, zz, -1.388731625493765e-3f), zz,
+                              4.166664568298827e-2f),
+                         zz * zz, fmaf(-0.5f, zz, 1.0f));
+    const bool odd = (static_cast<int>(q) & 1) != 0;
+    const float p2 = 2.0f * s * c;
+    sin2 = odd ? -p2 : p2;
+    ssq = odd ? c * c : s * s;
+}
+
+// ---------------------------------------------------------------- data gradient
+constexpr int kDgCT = 32;          // ci rows per workgroup (two MFMA row blocks)
+constexpr int kDgTN = 128;         // columns u per workgroup: 32 per wave (two column blocks)
+constexpr int kDgMC = 16;          // output channels m per staged K chunk
+constexpr int kDgXR = 176;         // gy window row stride: >= 128 + 2 * 16, 16 mod 32
+constexpr int kDgWR = 48;          // weight row stride: >= 32, 16 mod 32
+constexpr int kDgMaxNI = 7;        // taps per phase (k / s)
+static_assert(kDgXR % 32 == 16 && kDgWR % 32 == 16, "fragment reads: the two k rows of a half on disjoint banks");
+static_assert(kDgXR >= kDgTN + 2 * kMaxDil && kDgXR >= kDgTN + kDgMaxNI - 1, "window row");
+
+__global__ __launch_bounds__(256) void conv1d_grad_data_kernel(CgArgs a) {
+    __shared__ float gs[kDgMC * kDgXR];                   // [m][window column]
+    __shared__ float wsm[kDgMaxNI * kDgMC * kDgWR];       // [i][m][ci]
+    __shared__ float red[4 * kDgCT];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int kk = lane >> 4, col = lane & 15;
+    const int bz = blockIdx.z;
+    const int b = bz / a.s, p = bz - b * a.s;
+    const int j0 = (p + a.pl) % a.s, q = (p + a.pl) / a.s;
+    const int NI = a.k / a.s;
+    const int U = p < a.t_in ? (a.t_in - p + a.s - 1) / a.s : 0;   // columns of this phase
+    const int u0 = blockIdx.x * kDgTN, ci0 = blockIdx.y * kDgCT;
+    const bool want_alpha = a.act == RAVE_ACT_SNAKE && a.apart != nullptr;
+    float* aprow = want_alpha ? a.apart + ((int64_t)bz * gridDim.x + blockIdx.x) * a.c_in : nullptr;
+    if (u0 >= U) {                                        // uniform: an empty tile of a short phase
+        if (want_alpha && tid < kDgCT && ci0 + tid < a.c_in) aprow[ci0 + tid] = 0.f;
+        return;
+    }
+    const int XW = kDgTN + (NI - 1) * a.d;                // window columns
+    const int nw0 = u0 + q - (NI - 1) * a.d;              // n of window column 0
+    const float* gyb = a.gy + (int64_t)b * a.gy_sb;
+    const int wci = tid / NI, wi = tid - wci * NI;        // this thread's (ci, i) of the weight chunk
+
+    f32x4 acc[2][2];
+#pragma unroll
+    for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+        for (int cb = 0; cb < 2; ++cb) acc[rb][cb] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    for (int m0 = 0; m0 < a.c_out; m0 += kDgMC) {
+        __syncthreads();
+        {
+            float gv[kDgMC], wv[kDgMC];
+            const int n = nw0 + tid;
+            const bool nok = tid < XW && n >= 0 && n < a.t_out;
+            const bool wok = tid < kDgCT * NI && ci0 + wci < a.c_in;
+#pragma unroll
+            for (int m = 0; m < kDgMC; ++m) {
+                const bool mok = m0 + m < a.c_out;
+                gv[m] = (nok && mok) ? gyb[(int64_t)(m0 + m) * a.gy_sc + n] : 0.f;
+                wv[m] = (wok && mok) ? a.w[((int64_t)(m0 + m) * a.c_in + ci0 + wci) * a.k + j0 + a.s * wi] : 0.f;
+            }
+#pragma unroll
+            for (int m = 0; m < kDgMC; ++m) {
+                if (tid < XW) gs[m * kDgXR + tid] = gv[m];
+                if (tid < kDgCT * NI) wsm[(wi * kDgMC + m) * kDgWR + wci] = wv[m];
+            }
+        }
+        __syncthreads();
+        for (int i = 0; i < NI; ++i) {
+            const float* wa = wsm + (i * kDgMC + kk) * kDgWR + col;
+            const float* gb = gs + kk * kDgXR + wave * 32 + col + (NI - 1 - i) * a.d;
+#pragma unroll
+            for (int ms = 0; ms < kDgMC / 4; ++ms) {
+                const float a0 = wa[4 * ms * kDgWR], a1 = wa[4 * ms * kDgWR + 16];
+                const float b0 = gb[4 * ms * kDgXR], b1 = gb[4 * ms * kDgXR + 16];
+                acc[0][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b0, acc[0][0], 0, 0, 0);
+                acc[0][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b1, acc[0][1], 0, 0, 0);
+                acc[1][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b0, acc[1][0], 0, 0, 0);
+                acc[1][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b1, acc[1][1], 0, 0, 0);
+            }
+        }
+    }
+
+    // D: row ci = 4 kk + r of the row block, column = col of the column block
+    const float* xb = a.x ? a.x + (int64_t)b * a.x_sb : nullptr;
+    float* gxb = a.gx ? a.gx + (int64_t)b * a.gx_sb : nullptr;
+    float asum[2][4];
+#pragma unroll
+    for (int rb = 0; rb < 2; ++rb) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int ci = ci0 + rb * 16 + 4 * kk + r;
+            const bool cok = ci < a.c_in;
+            float al = 0.f, rr = 0.f;
+            if (a.act == RAVE_ACT_SNAKE) {
+                al = a.alpha[cok ? ci : 0];
+                rr = 1.0f / (al + 1e-9f);
+            }
+            float sum = 0.f;
+#pragma unroll
+            for (int cb = 0; cb < 2; ++cb) {
+                const int u = u0 + wave * 32 + cb * 16 + col;
+                const int64_t t = (int64_t)u * a.s + p;
+                const bool ok = cok && t < a.t_in;
+                const float ga = acc[rb][cb][r];
+                float g = ga;
+                if (a.act != RAVE_ACT_NONE) {
+                    const float xv = ok ? xb[(int64_t)ci * a.x_sc + t] : 0.f;
+                    if (a.act == RAVE_ACT_LEAKY) {
+                        g = xv > 0.f ? ga : ga * a.slope;
+                    } else {
+                        float sin2, ssq;
+                        snake_parts(al * xv, sin2, ssq);
+                        g = ga * fmaf(al * rr, sin2, 1.0f);
+                        const float da = (xv * sin2) * rr - (ssq * rr) * rr;
+                        sum += ok ? ga * da : 0.f;
+                    }
+                }
+                if (ok && gxb) gxb[(int64_t)ci * a.gx_sc + t] = g;
+            }
+            asum[rb][r] = sum;
+        }
+    }
+    if (want_alpha) {                                     // uniform
+#pragma unroll
+        for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                float v = asum[rb][r];
+#pragma unroll
+                for (int o = 1; o < 16; o <<= 1) v += __shfl_xor(v, o);
+                if (col == 0) red[wave * kDgCT + rb * 16 + 4 * kk + r] = v;
+            }
+        __syncthreads();
+        if (tid < kDgCT && ci0 + tid < a.c_in)
+            aprow[ci0 + tid] = ((red[tid] + red[kDgCT + tid]) + red[2 * kDgCT + tid]) + red[3 * kDgCT + tid];
+    }
+}
+
+// galpha[ci] = the partial rows in row order: one wave per ci, lane l takes rows
+// l, l + 64, ... in order, then a fixed butterfly.
+__global__ __launch_bounds__(64) void conv1d_grad_alpha_reduce_kernel(CgArgs a) {
+    const int ci = blockIdx.x, lane = threadIdx.x;
+    float v = 0.f;
+    for (int r = lane; r < a.P; r += 64) v += a.apart[(int64_t)r * a.c_in + ci];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    if (lane == 0) a.galpha[ci] = v;
+}
+
+// ---------------------------------------------------------------- weight gradient
+constexpr int kWgMT = 64;          // rows m per workgroup: one MFMA row block per wave
+constexpr int kWgCT = 16;          // input channels per workgroup: one column block per tap
+constexpr int kWgTK = 64;          // output columns n per staged K chunk
+constexpr int kWgHR = 66;          // gy row stride: 2 x 33
+constexpr int wg_stride(int kt) { return kt == 4 ? 2 : kt == 8 ? 4 : 1; }
+// columns of the staged input window at the largest dilation, per phase, and the row stride (2 x odd)
+constexpr int wg_xwin(int kt) { return (kWgTK - 1) * wg_stride(kt) + (kt - 1) * (kt == 3 ? kMaxDil : 1) + 1; }
+constexpr int wg_pr(int kt) { return ceil_div(wg_xwin(kt), wg_stride(kt)); }
+constexpr int wg_xr(int kt) { return (wg_pr(kt) * wg_stride(kt) + 1) / 4 * 4 + 2; }
+static_assert(kWgHR % 4 == 2 && kWgHR >= kWgTK, "gy rows: banks 2 row' + k");
+
+template <int KT>
+__global__ __launch_bounds__(256) void conv1d_grad_weight_kernel(CgArgs a) {
+    constexpr int ST = wg_stride(KT), PR = wg_pr(KT), XR = wg_xr(KT);
+    static_assert(XR % 4 == 2 && XR >= PR * ST, "window rows: banks 2 row' + k");
+    static_assert(kWgTK - 1 + (KT - 1) / ST < PR || ST == 1, "phase row");
+    __shared__ float gys[kWgMT * kWgHR];                  // [m][n]
+    __shared__ float xs[kWgCT * XR];                      // [ci][phase][column / s], act applied
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int kk = lane >> 4, col = lane & 15;
+    const int m0 = blockIdx.x * kWgMT, ci0 = blockIdx.y * kWgCT, sp = blockIdx.z;
+    const int XW = (kWgTK - 1) * ST + (KT - 1) * a.d + 1;
+    f32x4 acc[KT];
+#pragma unroll
+    for (int j = 0; j < KT; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    float bsum = 0.f;
+    const int ch_end = min((sp + 1) * a.cps, a.nch);
+    for (int ch = sp * a.cps; ch < ch_end; ++ch) {
+        const int b = ch / a.tch;
+        const int n0 = (ch - b * a.tch) * kWgTK;
+        const float* gyb = a.gy + (int64_t)b * a.gy_sb;
+        const float* xb = a.x + (int64_t)b * a.x_sb;
+        const int tw0 = n0 * ST - a.pl;                   // t of window column 0
+        __syncthreads();
+        {
+            constexpr int GT = kWgMT * kWgTK / 256;
+            float gv[GT];
+#pragma unroll
+            for (int it = 0; it < GT; ++it) {
+                const int e = tid + it * 256;
+                const int m = m0 + (e >> 6), n = n0 + (e & 63);
+                gv[it] = (m < a.c_out && n < a.t_out) ? gyb[(int64_t)m * a.gy_sc + n] : 0.f;
+            }
+#pragma unroll
+            for (int it = 0; it < GT; ++it) {
+                const int e = tid + it * 256;
+                gys[(e >> 6) * kWgHR + (e & 63)] = gv[it];
+            }
+        }
+        for (int w = tid; w < XW; w += 256) {
+            const int t = tw0 + w;
+            // a column counts only if a valid output n < t_out reads it through some tap: the
+            // columns a stride's right tail or a dilation's gaps leave unread (a NaN there must
+            // not meet the zero cotangent of a masked n) stage as zeros.  Bias only: x unread.
+            bool used = false;
+#pragma unroll
+            for (int j = 0; j < KT; ++j) {
+                const int r = w - j * (ST == 1 ? a.d : 1);
+                if (r >= 0 && r % ST == 0 && r / ST < kWgTK && n0 + r / ST < a.t_out) used = true;
+            }
+            const bool tok = a.gw != nullptr && used && t >= 0 && t < a.t_in;
+            const int dst = (w % ST) * PR + w / ST;
+            float xv[kWgCT];
+#pragma unroll
+            for (int c = 0; c < kWgCT; ++c)
+                xv[c] = (tok && ci0 + c < a.c_in) ? xb[(int64_t)(ci0 + c) * a.x_sc + t] : 0.f;
+#pragma unroll
+            for (int c = 0; c < kWgCT; ++c) {
+                float v = xv[c];
+                if (a.act != RAVE_ACT_NONE && tok && ci0 + c < a.c_in)
+                    v = apply_act(v, a.act, a.slope, a.act == RAVE_ACT_SNAKE ? a.alpha[ci0 + c] : 0.f);
+                xs[c * XR + dst] = v;
+            }
+        }
+        __syncthreads();
+        const float* ga = gys + (wave * 16 + col) * kWgHR + kk;
+        const float* xa = xs + col * XR + kk;
+#pragma unroll 4
+        for (int st = 0; st < kWgTK / 4; ++st) {
+            const float av = ga[4 * st];
+            bsum += av;
+#pragma unroll
+            for (int j = 0; j < KT; ++j) {
+                const int off = ST == 1 ? j * a.d : (j % ST) * PR + j / ST;
+                acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, xa[off + 4 * st], acc[j], 0, 0, 0);
+            }
+        }
+    }
+    // D: row m = 4 kk + r of this wave's row block, column ci = col
+    const int NW = a.c_in * KT + 1;                       // slab row: c_in x k weights, then the bias
+    const bool direct = a.S == 1;
+    float* slab = direct ? nullptr : a.slabs + (int64_t)sp * a.c_out * NW;
+    const int ci = ci0 + col;
+    if (ci < a.c_in && (a.gw || !direct)) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int m = m0 + wave * 16 + 4 * kk + r;
+            if (m >= a.c_out) continue;
+#pragma unroll
+            for (int j = 0; j < KT; ++j) {
+                if (direct)
+                    a.gw[((int64_t)m * a.c_in + ci) * KT + j] = acc[j][r];
+                else
+                    slab[(int64_t)m * NW + ci * KT + j] = acc[j][r];
+            }
+        }
+    }
+    // gbias: this lane's A values are row `col`, k = kk: sum the four k lanes
+    bsum += __shfl_xor(bsum, 16);
+    bsum += __shfl_xor(bsum, 32);
+    if (blockIdx.y == 0 && lane < 16) {
+        const int m = m0 + wave * 16 + lane;
+        if (m < a.c_out) {
+            if (!direct)
+                slab[(int64_t)m * NW + NW - 1] = bsum;
+            else if (a.gb)
+                a.gb[m] = bsum;
+        }
+    }
+}
+
+// Sum the slabs in slab order into gweight (torch layout) and gbias.
+__global__ __launch_bounds__(256) void conv1d_grad_weight_reduce_kernel(CgArgs a) {
+    const int NW = a.c_in * a.k + 1;
+    const int64_t total = (int64_t)a.c_out * NW;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int m = (int)(i / NW);
+        const int c = (int)(i - (int64_t)m * NW);
+        const bool bias = c == NW - 1;
+        if (bias ? a.gb == nullptr : a.gw == nullptr) continue;
+        float v = 0.f;
+        for (int s = 0; s < a.S; ++s) v += a.slabs[(int64_t)s * total + i];
+        if (bias)
+            a.gb[m] = v;
+        else
+            a.gw[(int64_t)m * (NW - 1) + c] = v;
+    }
+}
+
+// ---------------------------------------------------------------- host side
+// The forward's refusals (conv_shared.h prepare_common) in its order, then this file's own.
+static int check_args(const rave_conv1d_backward_args* p) {
+    RAVE_CHECK_ARG(p, "conv1d_backward: null args");
+    const rave_conv1d_backward_args& a = *p;
+    RAVE_CHECK_ARG(a.precision == RAVE_PREC_F32, "conv1d_backward: precision must be RAVE_PREC_F32");
+    RAVE_CHECK_ARG(a.batch > 0 && a.t_in > 0 && a.t_out > 0 && a.c_in > 0 && a.c_out > 0,
+                   "conv1d_backward: empty shape");
+    RAVE_CHECK_ARG(a.act != RAVE_ACT_SNAKE || a.alpha, "conv1d_backward: snake needs alpha");
+    RAVE_CHECK_ARG(a.act >= RAVE_ACT_NONE && a.act <= RAVE_ACT_SNAKE, "conv1d_backward: unknown activation");
+    RAVE_CHECK_ARG(a.pad_left >= 0 && a.pad_right >= 0, "conv1d_backward: negative padding");
+    RAVE_CHECK_ARG(!a.transposed, "conv1d_backward: transposed convs have no backward yet");
+    if (!family_supported(a.kernel) || a.kernel == 2 || family_stride(a.kernel) != a.stride) {
+        set_error("conv1d_backward: unsupported (kernel, stride) pair; supported: k1/k3/k7 s1, k4 s2, k8 s4");
+        return RAVE_ERR_UNSUPPORTED;
+    }
+    RAVE_CHECK_ARG(a.dilation == 1 || a.kernel == 3, "conv1d_backward: dilation only on 3-tap convs");
+    RAVE_CHECK_ARG(a.dilation >= 1 && a.dilation <= kMaxDil, "conv1d_backward: dilation out of range");
+    const int span = (a.kernel - 1) * a.dilation + 1;
+    const int expect = (a.t_in + a.pad_left + a.pad_right - span) / a.stride + 1;
+    RAVE_CHECK_ARG(expect == a.t_out, "conv1d_backward: t_out does not match the conv arithmetic");
+    return RAVE_OK;
+}
+
+struct WgSplit {
+    int S, cps, nch, tch;
+};
+static WgSplit weight_split(const rave_conv1d_backward_args& a) {
+    WgSplit w;
+    w.tch = ceil_div(a.t_out, kWgTK);
+    w.nch = a.batch * w.tch;
+    const int tiles = ceil_div(a.c_out, kWgMT) * ceil_div(a.c_in, kWgCT);
+    // fill two workgroups per CU, each split at least four chunks (256 columns) long
+    int S = std::max(1, std::min(ceil_div(512, tiles), w.nch / 4));
+    w.cps = ceil_div(w.nch, S);
+    w.S = ceil_div(w.nch, w.cps);
+    return w;
+}
+static inline int64_t slab_floats(const rave_conv1d_backward_args& a) {
+    if (!a.gweight && !a.gbias) return 0;
+    const WgSplit w = weight_split(a);
+    return w.S > 1 ? (int64_t)w.S * a.c_out * ((int64_t)a.c_in * a.kernel + 1) : 0;
+}
+static inline dim3 data_grid(const rave_conv1d_backward_args& a) {
+    return dim3(ceil_div(ceil_div(a.t_in, a.stride), kDgTN), ceil_div(a.c_in, kDgCT), a.batch * a.stride);
+}
+static inline int64_t alpha_floats(const rave_conv1d_backward_args& a) {
+    if (a.act != RAVE_ACT_SNAKE || !a.galpha) return 0;
+    const dim3 g = data_grid(a);
+    return (int64_t)g.x * g.z * a.c_in;
+}
+
+static CgArgs kernel_args(const rave_conv1d_backward_args& a) {
+    CgArgs k{};
+    k.x = a.x; k.gy = a.gy; k.w = a.weight; k.alpha = a.alpha;
+    k.gx = a.gx; k.gw = a.gweight; k.gb = a.gbias; k.galpha = a.galpha;
+    k.x_sb = a.x_sb; k.x_sc = a.x_sc; k.gy_sb = a.gy_sb; k.gy_sc = a.gy_sc; k.gx_sb = a.gx_sb; k.gx_sc = a.gx_sc;
+    k.c_in = a.c_in; k.c_out = a.c_out; k.k = a.kernel; k.s = a.stride; k.d = a.dilation; k.pl = a.pad_left;
+    k.t_in = a.t_in; k.t_out = a.t_out; k.B = a.batch; k.act = a.act; k.slope = a.leaky_slope;
+    k.slabs = a.workspace;
+    k.apart = a.workspace ? a.workspace + slab_floats(a) : nullptr;
+    return k;
+}
+
+}  // namespace rave
+
+using namespace rave;
+
+extern "C" int64_t rave_conv1d_backward_workspace(const rave_conv1d_backward_args* p) {
+    const int rc = check_args(p);
+    if (rc != RAVE_OK) return rc;
+    return slab_floats(*p) + alpha_floats(*p);
+}
+
+extern "C" int rave_conv1d_backward_data(const rave_conv1d_backward_args* p, void* stream) {
+    const int rc = check_args(p);
+    if (rc != RAVE_OK) return rc;
+    const rave_conv1d_backward_args& a = *p;
+    const bool want_alpha = a.act == RAVE_ACT_SNAKE && a.galpha;
+    if (!a.gx && !want_alpha) return RAVE_OK;
+    RAVE_CHECK_ARG(a.gy && a.weight, "conv1d_backward_data: null gy or weight");
+    RAVE_CHECK_ARG(a.act == RAVE_ACT_NONE || a.x, "conv1d_backward_data: the activation's derivative needs the input x");
+    RAVE_CHECK_ARG(!want_alpha || a.workspace, "conv1d_backward_data: galpha needs the workspace");
+    RAVE_CHECK_ARG((int64_t)a.batch * a.stride <= 65535 && ceil_div(a.c_in, kDgCT) <= 65535,
+                   "conv1d_backward_data: grid beyond 65535 in y or z");
+    CgArgs k = kernel_args(a);
+    if (!want_alpha) k.apart = nullptr;
+    const dim3 grid = data_grid(a);
+    k.P = (int)(grid.x * grid.z);
+    launch(conv1d_grad_data_kernel, grid, dim3(256), 0, as_stream(stream), k);
+    int st = launch_status("conv1d_grad_data_kernel");
+    if (st != RAVE_OK || !want_alpha) return st;
+    launch(conv1d_grad_alpha_reduce_kernel, dim3(a.c_in), dim3(64), 0, as_stream(stream), k);
+    return launch_status("conv1d_grad_alpha_reduce_kernel");
+}
+
+extern "C" int rave_conv1d_backward_weight(const rave_conv1d_backward_args* p, void* stream) {
+    const int rc = check_args(p);
+    if (rc != RAVE_OK) return rc;
+    const rave_conv1d_backward_args& a = *p;
+    if (!a.gweight && !a.gbias) return RAVE_OK;
+    RAVE_CHECK_ARG(a.gy, "conv1d_backward_weight: null gy");
+    RAVE_CHECK_ARG(a.x || !a.gweight, "conv1d_backward_weight: gweight needs the input x");
+    const WgSplit w = weight_split(a);
+    RAVE_CHECK_ARG(w.S == 1 || a.workspace, "conv1d_backward_weight: the K split needs the workspace");
+    CgArgs k = kernel_args(a);
+    k.S = w.S; k.cps = w.cps; k.nch = w.nch; k.tch = w.tch;
+    // bias only: one ci tile carries the row sums (its weight columns are not stored / not summed)
+    const dim3 grid(ceil_div(a.c_out, kWgMT), a.gweight ? ceil_div(a.c_in, kWgCT) : 1, w.S);
+    RAVE_CHECK_ARG(grid.y <= 65535 && grid.z <= 65535, "conv1d_backward_weight: grid beyond 65535 in y or z");
+    hipStream_t st = as_stream(stream);
+    switch (a.kernel) {
+        case 1: launch(conv1d_grad_weight_kernel<1>, grid, dim3(256), 0, st, k); break;
+        case 3: launch(conv1d_grad_weight_kernel<3>, grid, dim3(256), 0, st, k); break;
+        case 7: launch(conv1d_grad_weight_kernel<7>, grid, dim3(256), 0, st, k); break;
+        case 4: launch(conv1d_grad_weight_kernel<4>, grid, dim3(256), 0, st, k); break;
+        default: launch(conv1d_grad_weight_kernel<8>, grid, dim3(256), 0, st, k); break;
+    }
+    int s = launch_status("conv1d_grad_weight_kernel");
+    if (s != RAVE_OK || w.S == 1) return s;
+    const int64_t total = (int64_t)a.c_out * ((int64_t)a.c_in * a.kernel + 1);
+    launch(conv1d_grad_weight_reduce_kernel, dim3((unsigned)std::min<int64_t>(1024, ceil_div64(total, 256))), dim3(256), 0,
+           st, k);
+    return launch_status("conv1d_grad_weight_reduce_kernel");
+}

@@ -395,6 +395,98 @@ at::Tensor conv1d_op(at::Tensor x, at::Tensor packed, c10::optional<at::Tensor> 
     return y;
 }
 
+// rave_amd::conv1d_backward -- the gradients of a non-transposed conv1d call on
+// rave_conv1d_backward_data / _weight (exact fp32): gy (B, c_out, t_out), the
+// forward's x (B, c_in, t_in; None where neither an activation's derivative nor
+// gweight reads it), the torch-layout weight (None where neither gx nor galpha
+// is asked for) and alpha -> (gx, gweight, gbias,
+// galpha), each None where its bit of `need` (1 x, 2 weight, 4 bias, 8 alpha) is clear.
+std::tuple<c10::optional<at::Tensor>, c10::optional<at::Tensor>, c10::optional<at::Tensor>, c10::optional<at::Tensor>>
+conv1d_backward_op(at::Tensor gy, c10::optional<at::Tensor> x_, c10::optional<at::Tensor> weight,
+                   c10::optional<at::Tensor> alpha, int64_t c_in, int64_t t_in, int64_t kernel, int64_t stride,
+                   int64_t dilation, int64_t pad_left, int64_t pad_right, int64_t act, double slope, int64_t need) {
+    seam_tensor(gy, "gy");
+    c10::hip::HIPGuard g((c10::DeviceIndex)gy.get_device());
+    const int64_t B = gy.size(0), c_out = gy.size(1), T = t_in;
+    // x: needed by an activation's derivative and by gweight; weight: by gx and galpha
+    const bool want_data = (need & 1) || ((need & 8) && act == RAVE_ACT_SNAKE);
+    TORCH_CHECK_VALUE(x_.has_value() || !(act != RAVE_ACT_NONE && want_data) && !(need & 2),
+                      "conv1d_backward: these gradients need the forward's input x");
+    TORCH_CHECK_VALUE(weight.has_value() || !want_data, "conv1d_backward: gx and galpha need the weight");
+    at::Tensor x, w;
+    if (x_.has_value()) {
+        x = *x_;
+        seam_tensor(x, "x");
+        TORCH_CHECK_VALUE(x.device() == gy.device() && x.size(0) == B && x.size(1) == c_in && x.size(2) == T,
+                          "x must be (B, c_in, t_in) on gy's device");
+    }
+    if (weight.has_value()) {
+        TORCH_CHECK_VALUE(weight->is_cuda() && weight->device() == gy.device() && weight->scalar_type() == at::kFloat &&
+                              weight->dim() == 3 && weight->size(0) == c_out && weight->size(1) == c_in &&
+                              weight->size(2) == kernel,
+                          "weight must be a float32 (c_out, c_in, kernel) tensor on gy's device");
+        w = weight->contiguous();
+    }
+    rave_conv1d_backward_args a{};
+    a.c_in = (int)c_in; a.c_out = (int)c_out; a.kernel = (int)kernel; a.stride = (int)stride; a.dilation = (int)dilation;
+    a.pad_left = (int)pad_left; a.pad_right = (int)pad_right; a.act = (int)act; a.leaky_slope = (float)slope;
+    a.batch = (int)B; a.t_in = (int)T; a.t_out = (int)gy.size(2); a.precision = RAVE_PREC_F32;
+    if (x.defined()) {
+        a.x = x.data_ptr<float>(); a.x_sb = x.stride(0); a.x_sc = x.stride(1);
+    }
+    a.gy = gy.data_ptr<float>(); a.gy_sb = gy.stride(0); a.gy_sc = gy.stride(1);
+    if (w.defined()) a.weight = w.data_ptr<float>();
+    at::Tensor ad;
+    const bool snake = act == RAVE_ACT_SNAKE;
+    if (snake) {
+        TORCH_CHECK_VALUE(alpha.has_value(), "Snake needs alpha");
+        ad = alpha->to(gy.device(), at::kFloat).contiguous();
+        TORCH_CHECK_VALUE(ad.numel() == c_in, "alpha must have c_in values");
+        a.alpha = ad.data_ptr<float>();
+    }
+    c10::optional<at::Tensor> gx, gw, gb, ga;
+    if ((need & 1)) {
+        gx = at::empty({B, c_in, T}, gy.options());
+        a.gx = gx->data_ptr<float>(); a.gx_sb = gx->stride(0); a.gx_sc = gx->stride(1);
+    }
+    if ((need & 2)) {
+        gw = at::empty({c_out, c_in, kernel}, gy.options());
+        a.gweight = gw->data_ptr<float>();
+    }
+    if ((need & 4)) {
+        gb = at::empty({c_out}, gy.options());
+        a.gbias = gb->data_ptr<float>();
+    }
+    if ((need & 8) && snake) {
+        ga = at::empty({c_in}, gy.options());
+        a.galpha = ga->data_ptr<float>();
+    }
+    const int64_t nws = rave_conv1d_backward_workspace(&a);
+    if (nws < 0) check((int)nws, "conv1d_backward");
+    at::Tensor ws;
+    if (nws > 0) {
+        ws = at::empty({nws}, gy.options());                 // slabs and partials: nothing to zero
+        a.workspace = ws.data_ptr<float>();
+    }
+    check(rave_conv1d_backward_data(&a, cur_stream(gy)), "conv1d_backward_data");
+    check(rave_conv1d_backward_weight(&a, cur_stream(gy)), "conv1d_backward_weight");
+    return std::make_tuple(gx, gw, gb, ga);
+}
+
+// rave_amd::conv1d_w -- conv1d with the torch-layout weight beside its packed
+// image, so autograd has an edge to the parameter: the plain kernel is conv1d_op
+// itself (same launch, same bits; `weight` is not read), the autograd
+// implementation below sends the cotangent through conv1d_backward.
+// Non-transposed convs only.
+at::Tensor conv1d_w_op(at::Tensor x, at::Tensor weight, at::Tensor packed, c10::optional<at::Tensor> bias,
+                       c10::optional<at::Tensor> alpha, c10::optional<at::Tensor> residual, int64_t c_out,
+                       int64_t kernel, int64_t stride, int64_t dilation, int64_t pad_left, int64_t pad_right,
+                       int64_t act, double slope, int64_t precision) {
+    (void)weight;
+    return conv1d_op(x, packed, bias, alpha, residual, c_out, kernel, stride, dilation, pad_left, pad_right, false, 0,
+                     act, slope, precision);
+}
+
 // rave_amd::pqmf_analysis -- CachedPQMF.forward (rave/pqmf.py:269-273): x (B, 1, T)
 // -> (B, n_out_bands, T / n_band); hkf (n_band, taps) on x's device
 at::Tensor pqmf_analysis_op(at::Tensor x, at::Tensor hkf, int64_t n_out_bands, int64_t pad_left, int64_t precision) {
@@ -598,6 +690,89 @@ at::Tensor pqmf_synthesis_autograd(at::Tensor x, at::Tensor hki, int64_t pad_lef
     return pqmf_synthesis_op(x, hki, pad_left, frames, frame0, precision, mode, noise);
 }
 
+// Autograd for conv1d_w: saves x, the weight and alpha; one backward op call
+// returns the gradients of x, weight, bias and alpha, and the residual gets the
+// cotangent itself.  Exact fp32 only; no double backward.
+struct Conv1dWFn : torch::autograd::Function<Conv1dWFn> {
+    static at::Tensor forward(torch::autograd::AutogradContext* ctx, at::Tensor x, at::Tensor weight, at::Tensor packed,
+                              c10::optional<at::Tensor> bias, c10::optional<at::Tensor> alpha,
+                              c10::optional<at::Tensor> residual, int64_t c_out, int64_t kernel, int64_t stride,
+                              int64_t dilation, int64_t pad_left, int64_t pad_right, int64_t act, double slope,
+                              int64_t precision) {
+        at::AutoDispatchBelowADInplaceOrView below;
+        // only what the backward can read: x for an activation's derivative (when x or alpha
+        // takes a gradient) and for gweight; the weight for gx and galpha
+        const bool snake = act == RAVE_ACT_SNAKE && alpha.has_value();
+        const bool data = x.requires_grad() || (snake && alpha->requires_grad());
+        const bool keep_x = weight.requires_grad() || (act != RAVE_ACT_NONE && data);
+        ctx->save_for_backward({keep_x ? x : at::Tensor(), data ? weight : at::Tensor(), snake ? *alpha : at::Tensor()});
+        ctx->saved_data["c_in"] = x.size(1);
+        ctx->saved_data["t_in"] = x.size(2);
+        ctx->saved_data["kernel"] = kernel;
+        ctx->saved_data["stride"] = stride;
+        ctx->saved_data["dilation"] = dilation;
+        ctx->saved_data["pad_left"] = pad_left;
+        ctx->saved_data["pad_right"] = pad_right;
+        ctx->saved_data["act"] = act;
+        ctx->saved_data["slope"] = slope;
+        ctx->saved_data["has_bias"] = bias.has_value();
+        ctx->saved_data["has_res"] = residual.has_value();
+        ctx->saved_data["has_alpha"] = alpha.has_value();
+        return conv1d_w_op(x, weight, packed, bias, alpha, residual, c_out, kernel, stride, dilation, pad_left, pad_right,
+                           act, slope, precision);
+    }
+    static torch::autograd::variable_list backward(torch::autograd::AutogradContext* ctx,
+                                                   torch::autograd::variable_list grads) {
+        no_double_backward("conv1d_w");
+        at::AutoDispatchBelowADInplaceOrView below;
+        const auto saved = ctx->get_saved_variables();
+        c10::optional<at::Tensor> alpha;
+        if (saved[2].defined()) alpha = saved[2];
+        const bool has_bias = ctx->saved_data["has_bias"].toBool(), has_res = ctx->saved_data["has_res"].toBool();
+        // needs_input_grad counts the tensors that were passed (an absent optional has no edge):
+        // x, weight, packed, then bias, alpha and residual where given
+        const bool has_alpha = ctx->saved_data["has_alpha"].toBool();
+        const int e_bias = 3, e_alpha = e_bias + (has_bias ? 1 : 0), e_res = e_alpha + (has_alpha ? 1 : 0);
+        const int64_t need = (ctx->needs_input_grad(0) ? 1 : 0) | (ctx->needs_input_grad(1) ? 2 : 0) |
+                             (has_bias && ctx->needs_input_grad(e_bias) ? 4 : 0) |
+                             (alpha.has_value() && ctx->needs_input_grad(e_alpha) ? 8 : 0);
+        at::Tensor gy = grads[0].contiguous();
+        auto opt = [](const at::Tensor& t) { return t.defined() ? c10::optional<at::Tensor>(t) : c10::nullopt; };
+        auto g = conv1d_backward_op(gy, opt(saved[0]), opt(saved[1]), alpha, ctx->saved_data["c_in"].toInt(),
+                                    ctx->saved_data["t_in"].toInt(), ctx->saved_data["kernel"].toInt(),
+                                    ctx->saved_data["stride"].toInt(), ctx->saved_data["dilation"].toInt(),
+                                    ctx->saved_data["pad_left"].toInt(), ctx->saved_data["pad_right"].toInt(),
+                                    ctx->saved_data["act"].toInt(), ctx->saved_data["slope"].toDouble(), need);
+        auto get = [](const c10::optional<at::Tensor>& t) { return t.has_value() ? *t : at::Tensor(); };
+        torch::autograd::variable_list out(15);
+        out[0] = get(std::get<0>(g));
+        out[1] = get(std::get<1>(g));
+        out[3] = get(std::get<2>(g));
+        out[4] = get(std::get<3>(g));
+        if (has_res && ctx->needs_input_grad(e_res)) out[5] = gy;
+        return out;
+    }
+};
+
+at::Tensor conv1d_w_autograd(at::Tensor x, at::Tensor weight, at::Tensor packed, c10::optional<at::Tensor> bias,
+                             c10::optional<at::Tensor> alpha, c10::optional<at::Tensor> residual, int64_t c_out,
+                             int64_t kernel, int64_t stride, int64_t dilation, int64_t pad_left, int64_t pad_right,
+                             int64_t act, double slope, int64_t precision) {
+    auto rg = [](const c10::optional<at::Tensor>& t) { return t.has_value() && t->requires_grad(); };
+    const bool any = x.requires_grad() || weight.requires_grad() || rg(bias) || rg(alpha) || rg(residual);
+    if (at::GradMode::is_enabled() && any) {
+        TORCH_CHECK_NOT_IMPLEMENTED(precision == RAVE_PREC_F32,
+                                    "conv1d_w: only the exact fp32 precision (0) is differentiable; got precision ",
+                                    precision, " with an input that requires grad");
+        seam_tensor(x, "x");
+        return Conv1dWFn::apply(x, weight, packed, bias, alpha, residual, c_out, kernel, stride, dilation, pad_left,
+                                pad_right, act, slope, precision);
+    }
+    at::AutoDispatchBelowADInplaceOrView below;
+    return conv1d_w_op(x, weight, packed, bias, alpha, residual, c_out, kernel, stride, dilation, pad_left, pad_right, act,
+                       slope, precision);
+}
+
 // rave_amd::adain -- AdaptiveInstanceNormalization.forward in eval mode
 // (rave/blocks.py:856-919) on rave_adain over the module's own buffers
 // (mean_x / std_x / mean_y / std_y (max_batch, C, 1), num_update_x / _y (1,)):
@@ -748,6 +923,13 @@ TORCH_LIBRARY(rave_amd, lib) {
     lib.def("conv1d(Tensor x, Tensor packed, Tensor? bias, Tensor? alpha, Tensor? residual, int c_out, int kernel, "
             "int stride, int dilation, int pad_left, int pad_right, bool transposed, int out_shift, int act, "
             "float slope, int precision) -> Tensor", &conv1d_op);
+    lib.def("conv1d_w(Tensor x, Tensor weight, Tensor packed, Tensor? bias, Tensor? alpha, Tensor? residual, int c_out, "
+            "int kernel, int stride, int dilation, int pad_left, int pad_right, int act, float slope, int precision) "
+            "-> Tensor", &conv1d_w_op);
+    lib.def("conv1d_backward(Tensor gy, Tensor? x, Tensor? weight, Tensor? alpha, int c_in, int t_in, int kernel, "
+            "int stride, int dilation, "
+            "int pad_left, int pad_right, int act, float slope, int need) -> (Tensor? gx, Tensor? gweight, "
+            "Tensor? gbias, Tensor? galpha)", &conv1d_backward_op);
     lib.def("pqmf_analysis(Tensor x, Tensor hkf, int n_out_bands, int pad_left, int precision) -> Tensor",
             &pqmf_analysis_op);
     lib.def("pqmf_synthesis(Tensor x, Tensor hki, int pad_left, int frames, int frame0, int precision, int mode=0, "
@@ -803,4 +985,5 @@ TORCH_LIBRARY(rave_amd, lib) {
 TORCH_LIBRARY_IMPL(rave_amd, AutogradCUDA, m) {
     m.impl("pqmf_analysis", &pqmf_analysis_autograd);
     m.impl("pqmf_synthesis", &pqmf_synthesis_autograd);
+    m.impl("conv1d_w", &conv1d_w_autograd);
 }
