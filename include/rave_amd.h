@@ -328,8 +328,8 @@ int rave_pqmf_analysis_backward(const rave_pqmf_analysis_backward_args* a, void*
 typedef struct rave_conv1d_backward_args {
     int32_t c_in, c_out, kernel, stride, dilation;
     int32_t pad_left, pad_right;
-    int32_t transposed;     /* must be 0                                         */
-    int32_t out_shift;      /* unused                                            */
+    int32_t transposed;     /* 0 for rave_conv1d_backward_*, 1 for rave_conv_transpose1d_backward_* */
+    int32_t out_shift;      /* transposed: stride/2 (the offline geometry); else unused */
     int32_t act;            /* RAVE_ACT_*                                        */
     float   leaky_slope;
     int32_t batch, t_in, t_out;
@@ -348,6 +348,36 @@ typedef struct rave_conv1d_backward_args {
 int64_t rave_conv1d_backward_workspace(const rave_conv1d_backward_args* a);
 int rave_conv1d_backward_data(const rave_conv1d_backward_args* a, void* stream);
 int rave_conv1d_backward_weight(const rave_conv1d_backward_args* a, void* stream);
+
+/* ---------------------------------------------------------------- conv_transpose1d backward
+ * The backward of the offline transposed rave_conv1d (conv_grad.hip; added under
+ * ABI 21, nothing existing changed): autograd through cc.ConvTranspose1d, its
+ * fused input activation and bias.  Exact fp32 only.  The struct is
+ * rave_conv1d_backward_args with transposed = 1, kernel = 2 r, stride = r (2 or 4),
+ * pad_left = 0, out_shift = r/2 and t_out = t_in r: nn.ConvTranspose1d(c_in,
+ * c_out, 2 r, stride = r, padding = r/2).  dilation and pad_right are ignored.
+ * With a = act(x), P = r/2 and W in torch's layout (c_in, c_out, 2 r):
+ *   gbias[m]          = sum_{b, t} gy[b, m, t]
+ *   gweight[ci, m, j] = sum_{b, u} a[b, ci, u] * gy[b, m, u r + j - P]
+ *   ga[b, ci, u]      = sum_{m, j} W[ci, m, j] * gy[b, m, u r + j - P]
+ *                       (both over 0 <= u r + j - P < t_out)
+ *   gx                = ga * act'(x)
+ *   galpha[ci]        = sum_{b, u} ga[b, ci, u] * d act / d alpha (x[b, ci, u])   (Snake)
+ * with act' and d act / d alpha as above.
+ *
+ * weight and gweight are (c_in, c_out, 2 r), torch layout, read from and written
+ * to device memory as they are: no packed image on this path.  Strides, NULL
+ * outputs, the NULL x and the workspace follow rave_conv1d_backward_*: the
+ * workspace holds the weight gradient's split-K slabs (0 floats when it runs
+ * unsplit) and, for a Snake galpha, one row of c_in partials per data-kernel
+ * workgroup column; nothing in it needs zeroing, no atomics, two calls agree
+ * bit for bit.  transposed = 0, kernel != 2 stride, the cached geometry
+ * (pad_left = 1 / out_shift = 0) and any precision but RAVE_PREC_F32 return
+ * RAVE_ERR_ARG; a stride other than 2 or 4 returns RAVE_ERR_UNSUPPORTED.
+ */
+int64_t rave_conv_transpose1d_backward_workspace(const rave_conv1d_backward_args* a);
+int rave_conv_transpose1d_backward_data(const rave_conv1d_backward_args* a, void* stream);     /* gx, galpha */
+int rave_conv_transpose1d_backward_weight(const rave_conv1d_backward_args* a, void* stream);   /* gweight, gbias */
 
 /* ---------------------------------------------------------------- misc */
 /* y[b, c, t] = values[b * values_sb + c] for c < channels, t < t_len (speaker

@@ -314,7 +314,8 @@ EXPORTS = [
     "rave_last_error", "rave_abi_version", "rave_struct_sizes",
     "rave_conv1d_chunk", "rave_conv1d_packed_size", "rave_conv1d_pack_weight", "rave_conv1d",
     "rave_conv1d_workspace", "rave_conv1d_backward_workspace", "rave_conv1d_backward_data",
-    "rave_conv1d_backward_weight", "rave_conv1d_configs", "rave_conv1d_split_packed_size", "rave_conv1d_split_pack_weight",
+    "rave_conv1d_backward_weight", "rave_conv_transpose1d_backward_workspace", "rave_conv_transpose1d_backward_data",
+    "rave_conv_transpose1d_backward_weight", "rave_conv1d_configs", "rave_conv1d_split_packed_size", "rave_conv1d_split_pack_weight",
     "rave_conv1d_ring_pack_weight", "rave_conv1d_bf3_packed_size", "rave_conv1d_bf3_pack_weight",
     "rave_pqmf_analysis", "rave_pqmf_synthesis", "rave_pqmf_analysis_backward", "rave_pqmf_synthesis_backward",
     "rave_fill_channels", "rave_copy",
@@ -395,6 +396,8 @@ def _load():
     lib.rave_conv1d_workspace.restype = i64
     lib.rave_conv1d_backward_workspace.argtypes = [C.POINTER(ConvBackwardArgs)]
     lib.rave_conv1d_backward_workspace.restype = i64
+    lib.rave_conv_transpose1d_backward_workspace.argtypes = [C.POINTER(ConvBackwardArgs)]
+    lib.rave_conv_transpose1d_backward_workspace.restype = i64
     lib.rave_rvq_workspace.argtypes = [C.POINTER(RvqArgs)]
     lib.rave_rvq_workspace.restype = i64
     for name, st in [("rave_conv1d", ConvArgs), ("rave_pqmf_analysis", AnalysisArgs),
@@ -403,6 +406,8 @@ def _load():
                      ("rave_pqmf_analysis_backward", AnalysisBackwardArgs),
                      ("rave_conv1d_backward_data", ConvBackwardArgs),
                      ("rave_conv1d_backward_weight", ConvBackwardArgs),
+                     ("rave_conv_transpose1d_backward_data", ConvBackwardArgs),
+                     ("rave_conv_transpose1d_backward_weight", ConvBackwardArgs),
                      ("rave_rvq_encode", RvqArgs), ("rave_rvq_decode", RvqArgs),
                      ("rave_shift_history", ShiftArgs), ("rave_copy", CopyArgs),
                      ("rave_noise_synth", NoiseArgs), ("rave_adain", AdainArgs),

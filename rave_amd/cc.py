@@ -43,6 +43,7 @@ MAX_BATCH_SIZE = 64
 _USE_CACHED = False
 _PAD_MODE = "centered"
 _PRECISION = 0           # RAVE_PREC_F32; 1 = RAVE_PREC_SPLIT16 (include/rave_amd.h)
+_TRANSPOSED_GRAD = False
 ACT_NONE, ACT_LEAKY, ACT_SNAKE = 0, 1, 2
 
 
@@ -50,6 +51,13 @@ def use_cached_conv(state: bool) -> None:
     """cc.use_cached_conv: modules built afterwards take their cached form."""
     global _USE_CACHED
     _USE_CACHED = bool(state)
+
+
+def use_transposed_grad(state: bool) -> None:
+    """ConvTranspose1d modules built afterwards are differentiable (offline, exact
+    fp32, eager: ``rave_amd::conv_transpose1d_w``).  Off by default."""
+    global _TRANSPOSED_GRAD
+    _TRANSPOSED_GRAD = bool(state)
 
 
 def set_padding_mode(mode: str) -> None:
@@ -203,7 +211,16 @@ class Conv1d(_PackedConv):
 class ConvTranspose1d(_PackedConv):
     """cc.ConvTranspose1d(in, out, 2r, stride=r, padding=r//2): offline = torch's
     ConvTranspose1d; cached = CachedConvTranspose1d (overlap-add cache, output
-    delayed by r//2 samples)."""
+    delayed by r//2 samples).
+
+    Built under ``use_transposed_grad(True)`` (``self.differentiable``), the
+    offline exact-fp32 eager call is differentiable: it goes through
+    ``rave_amd::conv_transpose1d_w`` (the same kernel launch, same bits), whose
+    autograd implementation returns the gradients of x, ``weight``, ``bias``
+    and a Snake ``alpha`` from the transposed conv_grad kernels (r = 2 and 4).
+    Built by default, or cached, split16 or scripted, it calls
+    ``rave_amd::conv1d`` as before and carries no ``grad_fn``; there is no
+    double backward."""
 
     def __init__(self, in_channels: int, out_channels: int, kernel_size: int, stride: int = 1, padding: int = 0,
                  output_padding: int = 0, groups: int = 1, bias: bool = False, dilation: int = 1,
@@ -213,6 +230,7 @@ class ConvTranspose1d(_PackedConv):
         cached = _USE_CACHED
         super().__init__(in_channels, out_channels, kernel_size, stride, 1, True, 0 if cached else stride // 2, bias)
         self.cached = cached
+        self.differentiable = _TRANSPOSED_GRAD
         self.act, self.slope = int(activation), float(slope)
         self.register_buffer("alpha", torch.ones(in_channels) if activation == ACT_SNAKE else torch.zeros(0),
                              persistent=False)
@@ -231,6 +249,11 @@ class ConvTranspose1d(_PackedConv):
             pl = 1
         else:
             pl = 0
+            if self.differentiable and self.precision == 0 and not torch.jit.is_scripting():
+                # opted in, exact fp32, offline, eager: the same launch with an autograd edge to weight / bias / alpha
+                return torch.ops.rave_amd.conv_transpose1d_w(x.contiguous(), self.weight, packed, self.bias, alpha,
+                                                             residual, self.c_out, self.kernel, self.stride, act, slope,
+                                                             self.precision)
         return torch.ops.rave_amd.conv1d(x.contiguous(), packed, self.bias, alpha, residual, self.c_out, self.kernel,
                                          self.stride, 1, pl, 0, True, self.out_shift, act, slope, self.precision)
 

@@ -1,5 +1,6 @@
-// Backward of the non-transposed rave_conv1d (gfx950), exact fp32 only: the data
-// gradient, the weight / bias gradient and Snake's alpha gradient.
+// Backward of rave_conv1d (gfx950), exact fp32 only: the data gradient, the
+// weight / bias gradient and Snake's alpha gradient, of the non-transposed conv
+// (first) and of the offline ConvTranspose1d (its own section below).
 //
 // With a = act(x), zero outside [0, t_in), and the forward
 //   y[b, m, n] = bias[m] + sum_{ci, j} W[m, ci, j] a[b, ci, n s + j d - pl]  (+ res[b, m, n])
@@ -338,6 +339,288 @@ __global__ __launch_bounds__(256) void conv1d_grad_weight_reduce_kernel(CgArgs a
     }
 }
 
+// ---------------------------------------------------------------- transposed conv
+// Backward of the offline ConvTranspose1d(c_in, c_out, 2 r, stride r, padding r/2), r = 2 or 4,
+// W in torch's layout (c_in, c_out, 2 r), P = r/2:
+//   ga[b, ci, u]  = sum_{m, j} W[ci, m, j] gy[b, m, u r + j - P]           gx = ga act'(x)
+//   gW[ci, m, j]  = sum_{b, u} a[b, ci, u] gy[b, m, u r + j - P]           gbias[m] = sum_{b, t} gy[b, m, t]
+// Both kernels stage their gy window de-interleaved by phase: window column w (t = (u0 - 1) r + w)
+// sits at [m][w mod r][w / r], so tap j of column u is phase q(j) = (j + r/2) mod r at index
+// (u - u0) + sh(j), sh(j) = (j + r/2) / r in {0, 1, 2}: a fragment walks u at stride 1.
+//
+// data:   rows ci, columns u, K = (m, j) with the four k of an MFMA four taps of one m: the A
+//         fragment is then four consecutive floats of W's own row, and the weight chunk is a
+//         straight copy of 16 m x 2 r floats per ci row (row stride 2 x odd: banks 2 ci' + k).
+//         The B fragment's two k of a 32-lane half are taps j, j + 1 (j even), whose window rows
+//         differ by the phase stride (r = 4) or by 1 - the phase stride (r = 2): a phase stride
+//         of 16 (r = 4) or 17 (r = 2) mod 32 puts them on disjoint banks.
+// weight: rows ci (the operand that takes the activation), columns (j, m) in one block of 16 m
+//         per tap, K = (b, u) in chunks of 64 u; split and summed like the weight kernel above.
+//         gbias: the taps with sh(j) = 1 cover each phase of the chunk's own r x 64 columns
+//         exactly once, so the lanes sum the B fragments they feed the MFMAs: no pass over gy.
+template <int R> struct Tc {
+    static constexpr int K = 2 * R;
+    __host__ __device__ static constexpr int q(int j) { return (j + R / 2) % R; }
+    __host__ __device__ static constexpr int sh(int j) { return (j + R / 2) / R; }
+};
+
+constexpr int kTdCT = 32;          // ci rows per workgroup (two MFMA row blocks)
+constexpr int kTdTN = 128;         // columns u per workgroup: 32 per wave (two column blocks)
+constexpr int kTdMC = 16;          // output channels m per staged K chunk
+constexpr int kTdPC = kTdTN + 2;   // window indices per phase
+constexpr int td_pr(int r) { return r == 2 ? 145 : 144; }            // phase row stride
+constexpr int td_wr(int r) { return kTdMC * 2 * r + 2; }             // weight row stride
+static_assert(td_pr(4) % 32 == 16 && td_pr(2) % 32 == 17 && td_pr(2) >= kTdPC && td_pr(4) >= kTdPC, "window banks");
+static_assert(td_wr(2) % 4 == 2 && td_wr(4) % 4 == 2, "weight rows: banks 2 row' + k");
+
+template <int R>
+__global__ __launch_bounds__(256) void convt1d_grad_data_kernel(CgArgs a) {
+    using G = Tc<R>;
+    constexpr int K = G::K, PR = td_pr(R), XR = R * PR, WR = td_wr(R), MK = kTdMC * K;
+    __shared__ float gs[kTdMC * XR];                      // [m][phase][index]
+    __shared__ float wsm[kTdCT * WR];                     // [ci][m][j]: W's rows as they are
+    __shared__ float red[4 * kTdCT];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int kk = lane >> 4, col = lane & 15;
+    const int b = blockIdx.z;
+    const int u0 = blockIdx.x * kTdTN, ci0 = blockIdx.y * kTdCT;
+    const bool want_alpha = a.act == RAVE_ACT_SNAKE && a.apart != nullptr;
+    const float* gyb = a.gy + (int64_t)b * a.gy_sb;
+    const int64_t tw0 = ((int64_t)u0 - 1) * R;            // t of window column 0
+    int boff[K / 4];                                      // this lane's tap j = 4 jh + kk in the window
+#pragma unroll
+    for (int jh = 0; jh < K / 4; ++jh) {
+        const int j = 4 * jh + kk;
+        boff[jh] = ((j + R / 2) % R) * PR + (j + R / 2) / R + wave * 32 + col;
+    }
+
+    f32x4 acc[2][2];
+#pragma unroll
+    for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+        for (int cb = 0; cb < 2; ++cb) acc[rb][cb] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    for (int m0 = 0; m0 < a.c_out; m0 += kTdMC) {
+        __syncthreads();
+        {
+            constexpr int NG = ceil_div(kTdMC * R * kTdPC, 256), NWI = kTdCT * MK / 256;
+            float gv[NG], wv[NWI];
+#pragma unroll
+            for (int it = 0; it < NG; ++it) {
+                const int e = tid + it * 256;
+                const int m = e / (R * kTdPC), w = e - m * (R * kTdPC);
+                const int64_t t = tw0 + w;
+                const bool ok = m < kTdMC && m0 + m < a.c_out && t >= 0 && t < a.t_out;
+                gv[it] = ok ? gyb[(int64_t)(m0 + m) * a.gy_sc + t] : 0.f;
+            }
+#pragma unroll
+            for (int it = 0; it < NWI; ++it) {
+                const int e = tid + it * 256;
+                const int ci = e / MK, off = e - ci * MK;
+                const bool ok = ci0 + ci < a.c_in && m0 + off / K < a.c_out;
+                wv[it] = ok ? a.w[((int64_t)(ci0 + ci) * a.c_out + m0) * K + off] : 0.f;
+            }
+#pragma unroll
+            for (int it = 0; it < NG; ++it) {
+                const int e = tid + it * 256;
+                const int m = e / (R * kTdPC), w = e - m * (R * kTdPC);
+                if (m < kTdMC) gs[m * XR + (w % R) * PR + w / R] = gv[it];
+            }
+#pragma unroll
+            for (int it = 0; it < NWI; ++it) {
+                const int e = tid + it * 256;
+                const int ci = e / MK, off = e - ci * MK;
+                wsm[ci * WR + off] = wv[it];
+            }
+        }
+        __syncthreads();
+        const float* wa = wsm + col * WR + kk;
+#pragma unroll 4
+        for (int m = 0; m < kTdMC; ++m) {
+#pragma unroll
+            for (int jh = 0; jh < K / 4; ++jh) {
+                const float a0 = wa[m * K + 4 * jh], a1 = wa[16 * WR + m * K + 4 * jh];
+                const float b0 = gs[m * XR + boff[jh]], b1 = gs[m * XR + boff[jh] + 16];
+                acc[0][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b0, acc[0][0], 0, 0, 0);
+                acc[0][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b1, acc[0][1], 0, 0, 0);
+                acc[1][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b0, acc[1][0], 0, 0, 0);
+                acc[1][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b1, acc[1][1], 0, 0, 0);
+            }
+        }
+    }
+
+    // D: row ci = 4 kk + r of the row block, column u = col of the column block
+    const float* xb = a.x ? a.x + (int64_t)b * a.x_sb : nullptr;
+    float* gxb = a.gx ? a.gx + (int64_t)b * a.gx_sb : nullptr;
+    float asum[2][4];
+#pragma unroll
+    for (int rb = 0; rb < 2; ++rb) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int ci = ci0 + rb * 16 + 4 * kk + r;
+            const bool cok = ci < a.c_in;
+            float al = 0.f, rr = 0.f;
+            if (a.act == RAVE_ACT_SNAKE) {
+                al = a.alpha[cok ? ci : 0];
+                rr = 1.0f / (al + 1e-9f);
+            }
+            float sum = 0.f;
+#pragma unroll
+            for (int cb = 0; cb < 2; ++cb) {
+                const int u = u0 + wave * 32 + cb * 16 + col;
+                const bool ok = cok && u < a.t_in;
+                const float ga = acc[rb][cb][r];
+                float g = ga;
+                if (a.act != RAVE_ACT_NONE) {
+                    const float xv = ok ? xb[(int64_t)ci * a.x_sc + u] : 0.f;
+                    if (a.act == RAVE_ACT_LEAKY) {
+                        g = xv > 0.f ? ga : ga * a.slope;
+                    } else {
+                        float sin2, ssq;
+                        snake_parts(al * xv, sin2, ssq);
+                        g = ga * fmaf(al * rr, sin2, 1.0f);
+                        const float da = (xv * sin2) * rr - (ssq * rr) * rr;
+                        sum += ok ? ga * da : 0.f;
+                    }
+                }
+                if (ok && gxb) gxb[(int64_t)ci * a.gx_sc + u] = g;
+            }
+            asum[rb][r] = sum;
+        }
+    }
+    if (want_alpha) {                                     // uniform
+        float* aprow = a.apart + ((int64_t)b * gridDim.x + blockIdx.x) * a.c_in;
+#pragma unroll
+        for (int rb = 0; rb < 2; ++rb)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                float v = asum[rb][r];
+#pragma unroll
+                for (int o = 1; o < 16; o <<= 1) v += __shfl_xor(v, o);
+                if (col == 0) red[wave * kTdCT + rb * 16 + 4 * kk + r] = v;
+            }
+        __syncthreads();
+        if (tid < kTdCT && ci0 + tid < a.c_in)
+            aprow[ci0 + tid] = ((red[tid] + red[kTdCT + tid]) + red[2 * kTdCT + tid]) + red[3 * kTdCT + tid];
+    }
+}
+
+constexpr int kTwCT = 64;          // rows ci per workgroup: one MFMA row block per wave
+constexpr int kTwMT = 16;          // output channels per workgroup: one column block per tap
+constexpr int kTwTK = 64;          // input columns u per staged K chunk
+constexpr int kTwXR = 66;          // input row stride: 2 x 33
+constexpr int kTwPC = kTwTK + 2;   // window indices per phase
+constexpr int tw_gr(int r) { return r * kTwPC + 2; }                 // gy row stride per m
+static_assert(kTwXR % 4 == 2 && tw_gr(2) % 4 == 2 && tw_gr(4) % 4 == 2, "rows: banks 2 row' + k");
+
+template <int R>
+__global__ __launch_bounds__(256) void convt1d_grad_weight_kernel(CgArgs a) {
+    using G = Tc<R>;
+    constexpr int K = G::K, GR = tw_gr(R);
+    __shared__ float xs[kTwCT * kTwXR];                   // [ci][u], act applied
+    __shared__ float gys[kTwMT * GR];                     // [m][phase][index]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int kk = lane >> 4, col = lane & 15;
+    const int ci0 = blockIdx.x * kTwCT, m0 = blockIdx.y * kTwMT, sp = blockIdx.z;
+    f32x4 acc[K];
+#pragma unroll
+    for (int j = 0; j < K; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    float bsum = 0.f;
+    const int ch_end = min((sp + 1) * a.cps, a.nch);
+    for (int ch = sp * a.cps; ch < ch_end; ++ch) {
+        const int b = ch / a.tch;
+        const int u0 = (ch - b * a.tch) * kTwTK;
+        const float* gyb = a.gy + (int64_t)b * a.gy_sb;
+        const float* xb = a.x ? a.x + (int64_t)b * a.x_sb : nullptr;
+        const int64_t tw0 = ((int64_t)u0 - 1) * R;        // t of window column 0
+        __syncthreads();
+        {
+            constexpr int XT = kTwCT * kTwTK / 256, NG = ceil_div(kTwMT * R * kTwPC, 256);
+            float xv[XT], gv[NG];
+#pragma unroll
+            for (int it = 0; it < XT; ++it) {
+                const int e = tid + it * 256;
+                const int ci = ci0 + (e >> 6), u = u0 + (e & 63);
+                const bool ok = a.gw != nullptr && ci < a.c_in && u < a.t_in;     // bias only: x unread
+                float v = ok ? xb[(int64_t)ci * a.x_sc + u] : 0.f;
+                if (a.act != RAVE_ACT_NONE && ok)
+                    v = apply_act(v, a.act, a.slope, a.act == RAVE_ACT_SNAKE ? a.alpha[ci] : 0.f);
+                xv[it] = v;
+            }
+#pragma unroll
+            for (int it = 0; it < NG; ++it) {
+                const int e = tid + it * 256;
+                const int m = e / (R * kTwPC), w = e - m * (R * kTwPC);
+                const int64_t t = tw0 + w;
+                const bool ok = m < kTwMT && m0 + m < a.c_out && t >= 0 && t < a.t_out;
+                gv[it] = ok ? gyb[(int64_t)(m0 + m) * a.gy_sc + t] : 0.f;
+            }
+#pragma unroll
+            for (int it = 0; it < XT; ++it) {
+                const int e = tid + it * 256;
+                xs[(e >> 6) * kTwXR + (e & 63)] = xv[it];
+            }
+#pragma unroll
+            for (int it = 0; it < NG; ++it) {
+                const int e = tid + it * 256;
+                const int m = e / (R * kTwPC), w = e - m * (R * kTwPC);
+                if (m < kTwMT) gys[m * GR + (w % R) * kTwPC + w / R] = gv[it];
+            }
+        }
+        __syncthreads();
+        const float* xa = xs + (wave * 16 + col) * kTwXR + kk;
+        const float* gb = gys + col * GR + kk;
+#pragma unroll 2
+        for (int st = 0; st < kTwTK / 4; ++st) {
+            const float av = xa[4 * st];
+#pragma unroll
+            for (int j = 0; j < K; ++j) {
+                const float bv = gb[G::q(j) * kTwPC + G::sh(j) + 4 * st];
+                if (G::sh(j) == 1) bsum += bv;            // the chunk's own columns of phase q(j)
+                acc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, acc[j], 0, 0, 0);
+            }
+        }
+    }
+    // D: row ci = 4 kk + r of this wave's row block, column m = col
+    const int64_t WN = (int64_t)a.c_in * a.c_out * K;     // slab: the weights, then c_out bias sums
+    const bool direct = a.S == 1;
+    float* dst = direct ? a.gw : a.slabs + (int64_t)sp * (WN + a.c_out);
+    const int m = m0 + col;
+    if (a.gw && m < a.c_out) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int ci = ci0 + wave * 16 + 4 * kk + r;
+            if (ci >= a.c_in) continue;
+#pragma unroll
+            for (int j = 0; j < K; ++j) dst[((int64_t)ci * a.c_out + m) * K + j] = acc[j][r];
+        }
+    }
+    // gbias: this lane's B values are column `col`, k = kk: sum the four k lanes
+    bsum += __shfl_xor(bsum, 16);
+    bsum += __shfl_xor(bsum, 32);
+    if (blockIdx.x == 0 && wave == 0 && lane < 16 && m < a.c_out) {
+        if (!direct)
+            dst[WN + m] = bsum;
+        else if (a.gb)
+            a.gb[m] = bsum;
+    }
+}
+
+// Sum the slabs in slab order into gweight (torch layout (c_in, c_out, 2 r)) and gbias.
+__global__ __launch_bounds__(256) void convt1d_grad_weight_reduce_kernel(CgArgs a) {
+    const int64_t WN = (int64_t)a.c_in * a.c_out * a.k, total = WN + a.c_out;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const bool bias = i >= WN;
+        if (bias ? a.gb == nullptr : a.gw == nullptr) continue;
+        float v = 0.f;
+        for (int s = 0; s < a.S; ++s) v += a.slabs[(int64_t)s * total + i];
+        if (bias)
+            a.gb[i - WN] = v;
+        else
+            a.gw[i] = v;
+    }
+}
+
 // ---------------------------------------------------------------- host side
 // The forward's refusals (conv_shared.h prepare_common) in its order, then this file's own.
 static int check_args(const rave_conv1d_backward_args* p) {
@@ -402,9 +685,115 @@ static CgArgs kernel_args(const rave_conv1d_backward_args& a) {
     return k;
 }
 
+// ---- transposed: the offline geometry only, strides 2 and 4
+static int check_args_t(const rave_conv1d_backward_args* p) {
+    RAVE_CHECK_ARG(p, "conv_transpose1d_backward: null args");
+    const rave_conv1d_backward_args& a = *p;
+    RAVE_CHECK_ARG(a.precision == RAVE_PREC_F32, "conv_transpose1d_backward: precision must be RAVE_PREC_F32");
+    RAVE_CHECK_ARG(a.transposed == 1, "conv_transpose1d_backward: transposed must be 1 (rave_conv1d_backward_* takes the rest)");
+    RAVE_CHECK_ARG(a.batch > 0 && a.t_in > 0 && a.t_out > 0 && a.c_in > 0 && a.c_out > 0,
+                   "conv_transpose1d_backward: empty shape");
+    RAVE_CHECK_ARG(a.act >= RAVE_ACT_NONE && a.act <= RAVE_ACT_SNAKE, "conv_transpose1d_backward: unknown activation");
+    RAVE_CHECK_ARG(a.act != RAVE_ACT_SNAKE || a.alpha, "conv_transpose1d_backward: snake needs alpha");
+    RAVE_CHECK_ARG(a.stride > 0 && a.kernel == 2 * a.stride, "conv_transpose1d_backward: kernel must be 2 * stride");
+    RAVE_CHECK_ARG(a.pad_left == 0 && a.out_shift == a.stride / 2,
+                   "conv_transpose1d_backward: only the offline geometry (pad_left = 0, out_shift = stride/2); the "
+                   "cached form (pad_left = 1, out_shift = 0) has no backward");
+    if (a.stride != 2 && a.stride != 4) {
+        set_error("conv_transpose1d_backward: unsupported stride; supported: 2 and 4");
+        return RAVE_ERR_UNSUPPORTED;
+    }
+    RAVE_CHECK_ARG((int64_t)a.t_in * a.stride == a.t_out, "conv_transpose1d_backward: t_out must be t_in * stride");
+    return RAVE_OK;
+}
+
+static WgSplit weight_split_t(const rave_conv1d_backward_args& a) {
+    WgSplit w;
+    w.tch = ceil_div(a.t_in, kTwTK);
+    w.nch = a.batch * w.tch;
+    const int tiles = ceil_div(a.c_in, kTwCT) * ceil_div(a.c_out, kTwMT);
+    // (the same split with and without gweight: gbias keeps its bits)  fill two workgroups per CU, each split at least four chunks (256 input columns) long
+    int S = std::max(1, std::min(ceil_div(512, tiles), w.nch / 4));
+    w.cps = ceil_div(w.nch, S);
+    w.S = ceil_div(w.nch, w.cps);
+    return w;
+}
+static inline int64_t slab_floats_t(const rave_conv1d_backward_args& a) {
+    if (!a.gweight && !a.gbias) return 0;
+    const WgSplit w = weight_split_t(a);
+    return w.S > 1 ? (int64_t)w.S * ((int64_t)a.c_in * a.c_out * a.kernel + a.c_out) : 0;
+}
+static inline dim3 data_grid_t(const rave_conv1d_backward_args& a) {
+    return dim3(ceil_div(a.t_in, kTdTN), ceil_div(a.c_in, kTdCT), a.batch);
+}
+static inline int64_t alpha_floats_t(const rave_conv1d_backward_args& a) {
+    if (a.act != RAVE_ACT_SNAKE || !a.galpha) return 0;
+    const dim3 g = data_grid_t(a);
+    return (int64_t)g.x * g.z * a.c_in;
+}
+
 }  // namespace rave
 
 using namespace rave;
+
+extern "C" int64_t rave_conv_transpose1d_backward_workspace(const rave_conv1d_backward_args* p) {
+    const int rc = check_args_t(p);
+    if (rc != RAVE_OK) return rc;
+    return slab_floats_t(*p) + alpha_floats_t(*p);
+}
+
+extern "C" int rave_conv_transpose1d_backward_data(const rave_conv1d_backward_args* p, void* stream) {
+    const int rc = check_args_t(p);
+    if (rc != RAVE_OK) return rc;
+    const rave_conv1d_backward_args& a = *p;
+    const bool want_alpha = a.act == RAVE_ACT_SNAKE && a.galpha;
+    if (!a.gx && !want_alpha) return RAVE_OK;
+    RAVE_CHECK_ARG(a.gy && a.weight, "conv_transpose1d_backward_data: null gy or weight");
+    RAVE_CHECK_ARG(a.act == RAVE_ACT_NONE || a.x,
+                   "conv_transpose1d_backward_data: the activation's derivative needs the input x");
+    RAVE_CHECK_ARG(!want_alpha || a.workspace, "conv_transpose1d_backward_data: galpha needs the workspace");
+    const dim3 grid = data_grid_t(a);
+    RAVE_CHECK_ARG(grid.y <= 65535 && grid.z <= 65535, "conv_transpose1d_backward_data: grid beyond 65535 in y or z");
+    CgArgs k = kernel_args(a);
+    k.apart = want_alpha ? a.workspace + slab_floats_t(a) : nullptr;
+    k.P = (int)(grid.x * grid.z);
+    if (a.stride == 2)
+        launch(convt1d_grad_data_kernel<2>, grid, dim3(256), 0, as_stream(stream), k);
+    else
+        launch(convt1d_grad_data_kernel<4>, grid, dim3(256), 0, as_stream(stream), k);
+    int st = launch_status("convt1d_grad_data_kernel");
+    if (st != RAVE_OK || !want_alpha) return st;
+    launch(conv1d_grad_alpha_reduce_kernel, dim3(a.c_in), dim3(64), 0, as_stream(stream), k);
+    return launch_status("conv1d_grad_alpha_reduce_kernel");
+}
+
+extern "C" int rave_conv_transpose1d_backward_weight(const rave_conv1d_backward_args* p, void* stream) {
+    const int rc = check_args_t(p);
+    if (rc != RAVE_OK) return rc;
+    const rave_conv1d_backward_args& a = *p;
+    if (!a.gweight && !a.gbias) return RAVE_OK;
+    RAVE_CHECK_ARG(a.gy, "conv_transpose1d_backward_weight: null gy");
+    RAVE_CHECK_ARG(a.x || !a.gweight, "conv_transpose1d_backward_weight: gweight needs the input x");
+    const WgSplit w = weight_split_t(a);
+    RAVE_CHECK_ARG(w.S == 1 || a.workspace, "conv_transpose1d_backward_weight: the K split needs the workspace");
+    CgArgs k = kernel_args(a);
+    k.S = w.S; k.cps = w.cps; k.nch = w.nch; k.tch = w.tch;
+    // bias only: one ci tile carries the column sums (x is not read, no weight is stored)
+    const dim3 grid(a.gweight ? ceil_div(a.c_in, kTwCT) : 1, ceil_div(a.c_out, kTwMT), w.S);
+    RAVE_CHECK_ARG(grid.y <= 65535 && grid.z <= 65535,
+                   "conv_transpose1d_backward_weight: grid beyond 65535 in y or z");
+    hipStream_t st = as_stream(stream);
+    if (a.stride == 2)
+        launch(convt1d_grad_weight_kernel<2>, grid, dim3(256), 0, st, k);
+    else
+        launch(convt1d_grad_weight_kernel<4>, grid, dim3(256), 0, st, k);
+    int s = launch_status("convt1d_grad_weight_kernel");
+    if (s != RAVE_OK || w.S == 1) return s;
+    const int64_t total = (int64_t)a.c_in * a.c_out * a.kernel + a.c_out;
+    launch(convt1d_grad_weight_reduce_kernel, dim3((unsigned)std::min<int64_t>(1024, ceil_div64(total, 256))), dim3(256),
+           0, st, k);
+    return launch_status("convt1d_grad_weight_reduce_kernel");
+}
 
 extern "C" int64_t rave_conv1d_backward_workspace(const rave_conv1d_backward_args* p) {
     const int rc = check_args(p);

@@ -401,10 +401,16 @@ at::Tensor conv1d_op(at::Tensor x, at::Tensor packed, c10::optional<at::Tensor> 
 // gweight reads it), the torch-layout weight (None where neither gx nor galpha
 // is asked for) and alpha -> (gx, gweight, gbias,
 // galpha), each None where its bit of `need` (1 x, 2 weight, 4 bias, 8 alpha) is clear.
-std::tuple<c10::optional<at::Tensor>, c10::optional<at::Tensor>, c10::optional<at::Tensor>, c10::optional<at::Tensor>>
-conv1d_backward_op(at::Tensor gy, c10::optional<at::Tensor> x_, c10::optional<at::Tensor> weight,
-                   c10::optional<at::Tensor> alpha, int64_t c_in, int64_t t_in, int64_t kernel, int64_t stride,
-                   int64_t dilation, int64_t pad_left, int64_t pad_right, int64_t act, double slope, int64_t need) {
+//
+// transposed (rave_amd::conv_transpose1d_backward): the offline ConvTranspose1d(c_in, c_out,
+// 2 r, stride r, padding r/2) on rave_conv_transpose1d_backward_data / _weight; the weight
+// and gweight are then torch's (c_in, c_out, kernel).
+using ConvGrads =
+    std::tuple<c10::optional<at::Tensor>, c10::optional<at::Tensor>, c10::optional<at::Tensor>, c10::optional<at::Tensor>>;
+ConvGrads conv_backward_impl(at::Tensor gy, c10::optional<at::Tensor> x_, c10::optional<at::Tensor> weight,
+                             c10::optional<at::Tensor> alpha, int64_t c_in, int64_t t_in, int64_t kernel, int64_t stride,
+                             int64_t dilation, int64_t pad_left, int64_t pad_right, int64_t act, double slope,
+                             int64_t need, bool transposed) {
     seam_tensor(gy, "gy");
     c10::hip::HIPGuard g((c10::DeviceIndex)gy.get_device());
     const int64_t B = gy.size(0), c_out = gy.size(1), T = t_in;
@@ -422,12 +428,14 @@ conv1d_backward_op(at::Tensor gy, c10::optional<at::Tensor> x_, c10::optional<at
     }
     if (weight.has_value()) {
         TORCH_CHECK_VALUE(weight->is_cuda() && weight->device() == gy.device() && weight->scalar_type() == at::kFloat &&
-                              weight->dim() == 3 && weight->size(0) == c_out && weight->size(1) == c_in &&
-                              weight->size(2) == kernel,
-                          "weight must be a float32 (c_out, c_in, kernel) tensor on gy's device");
+                              weight->dim() == 3 && weight->size(0) == (transposed ? c_in : c_out) &&
+                              weight->size(1) == (transposed ? c_out : c_in) && weight->size(2) == kernel,
+                          "weight must be a float32 ", transposed ? "(c_in, c_out, kernel)" : "(c_out, c_in, kernel)",
+                          " tensor on gy's device");
         w = weight->contiguous();
     }
     rave_conv1d_backward_args a{};
+    a.transposed = transposed ? 1 : 0; a.out_shift = transposed ? (int)(stride / 2) : 0;
     a.c_in = (int)c_in; a.c_out = (int)c_out; a.kernel = (int)kernel; a.stride = (int)stride; a.dilation = (int)dilation;
     a.pad_left = (int)pad_left; a.pad_right = (int)pad_right; a.act = (int)act; a.leaky_slope = (float)slope;
     a.batch = (int)B; a.t_in = (int)T; a.t_out = (int)gy.size(2); a.precision = RAVE_PREC_F32;
@@ -450,7 +458,7 @@ conv1d_backward_op(at::Tensor gy, c10::optional<at::Tensor> x_, c10::optional<at
         a.gx = gx->data_ptr<float>(); a.gx_sb = gx->stride(0); a.gx_sc = gx->stride(1);
     }
     if ((need & 2)) {
-        gw = at::empty({c_out, c_in, kernel}, gy.options());
+        gw = transposed ? at::empty({c_in, c_out, kernel}, gy.options()) : at::empty({c_out, c_in, kernel}, gy.options());
         a.gweight = gw->data_ptr<float>();
     }
     if ((need & 4)) {
@@ -461,16 +469,35 @@ conv1d_backward_op(at::Tensor gy, c10::optional<at::Tensor> x_, c10::optional<at
         ga = at::empty({c_in}, gy.options());
         a.galpha = ga->data_ptr<float>();
     }
-    const int64_t nws = rave_conv1d_backward_workspace(&a);
-    if (nws < 0) check((int)nws, "conv1d_backward");
+    const int64_t nws = transposed ? rave_conv_transpose1d_backward_workspace(&a) : rave_conv1d_backward_workspace(&a);
+    if (nws < 0) check((int)nws, transposed ? "conv_transpose1d_backward" : "conv1d_backward");
     at::Tensor ws;
     if (nws > 0) {
         ws = at::empty({nws}, gy.options());                 // slabs and partials: nothing to zero
         a.workspace = ws.data_ptr<float>();
     }
-    check(rave_conv1d_backward_data(&a, cur_stream(gy)), "conv1d_backward_data");
-    check(rave_conv1d_backward_weight(&a, cur_stream(gy)), "conv1d_backward_weight");
+    if (transposed) {
+        check(rave_conv_transpose1d_backward_data(&a, cur_stream(gy)), "conv_transpose1d_backward_data");
+        check(rave_conv_transpose1d_backward_weight(&a, cur_stream(gy)), "conv_transpose1d_backward_weight");
+    } else {
+        check(rave_conv1d_backward_data(&a, cur_stream(gy)), "conv1d_backward_data");
+        check(rave_conv1d_backward_weight(&a, cur_stream(gy)), "conv1d_backward_weight");
+    }
     return std::make_tuple(gx, gw, gb, ga);
+}
+
+ConvGrads conv1d_backward_op(at::Tensor gy, c10::optional<at::Tensor> x, c10::optional<at::Tensor> weight,
+                             c10::optional<at::Tensor> alpha, int64_t c_in, int64_t t_in, int64_t kernel, int64_t stride,
+                             int64_t dilation, int64_t pad_left, int64_t pad_right, int64_t act, double slope,
+                             int64_t need) {
+    return conv_backward_impl(gy, x, weight, alpha, c_in, t_in, kernel, stride, dilation, pad_left, pad_right, act, slope,
+                              need, false);
+}
+
+ConvGrads conv_transpose1d_backward_op(at::Tensor gy, c10::optional<at::Tensor> x, c10::optional<at::Tensor> weight,
+                                       c10::optional<at::Tensor> alpha, int64_t c_in, int64_t t_in, int64_t kernel,
+                                       int64_t stride, int64_t act, double slope, int64_t need) {
+    return conv_backward_impl(gy, x, weight, alpha, c_in, t_in, kernel, stride, 1, 0, 0, act, slope, need, true);
 }
 
 // rave_amd::conv1d_w -- conv1d with the torch-layout weight beside its packed
@@ -485,6 +512,17 @@ at::Tensor conv1d_w_op(at::Tensor x, at::Tensor weight, at::Tensor packed, c10::
     (void)weight;
     return conv1d_op(x, packed, bias, alpha, residual, c_out, kernel, stride, dilation, pad_left, pad_right, false, 0,
                      act, slope, precision);
+}
+
+// rave_amd::conv_transpose1d_w -- the same for the offline ConvTranspose1d(c_in, c_out, 2 r,
+// stride r, padding r/2): conv1d_op's transposed launch on the packed image (out_shift
+// stride/2), with the torch-layout (c_in, c_out, kernel) weight beside it for autograd.
+at::Tensor conv_transpose1d_w_op(at::Tensor x, at::Tensor weight, at::Tensor packed, c10::optional<at::Tensor> bias,
+                                 c10::optional<at::Tensor> alpha, c10::optional<at::Tensor> residual, int64_t c_out,
+                                 int64_t kernel, int64_t stride, int64_t act, double slope, int64_t precision) {
+    (void)weight;
+    return conv1d_op(x, packed, bias, alpha, residual, c_out, kernel, stride, 1, 0, 0, true, stride / 2, act, slope,
+                     precision);
 }
 
 // rave_amd::pqmf_analysis -- CachedPQMF.forward (rave/pqmf.py:269-273): x (B, 1, T)
@@ -690,7 +728,8 @@ at::Tensor pqmf_synthesis_autograd(at::Tensor x, at::Tensor hki, int64_t pad_lef
     return pqmf_synthesis_op(x, hki, pad_left, frames, frame0, precision, mode, noise);
 }
 
-// Autograd for conv1d_w: saves x, the weight and alpha; one backward op call
+// Autograd for conv1d_w and conv_transpose1d_w (`transposed`; dilation 1 and no padding
+// arguments there): saves x, the weight and alpha; one backward op call
 // returns the gradients of x, weight, bias and alpha, and the residual gets the
 // cotangent itself.  Exact fp32 only; no double backward.
 struct Conv1dWFn : torch::autograd::Function<Conv1dWFn> {
@@ -698,7 +737,7 @@ struct Conv1dWFn : torch::autograd::Function<Conv1dWFn> {
                               c10::optional<at::Tensor> bias, c10::optional<at::Tensor> alpha,
                               c10::optional<at::Tensor> residual, int64_t c_out, int64_t kernel, int64_t stride,
                               int64_t dilation, int64_t pad_left, int64_t pad_right, int64_t act, double slope,
-                              int64_t precision) {
+                              int64_t precision, bool transposed) {
         at::AutoDispatchBelowADInplaceOrView below;
         // only what the backward can read: x for an activation's derivative (when x or alpha
         // takes a gradient) and for gweight; the weight for gx and galpha
@@ -718,12 +757,17 @@ struct Conv1dWFn : torch::autograd::Function<Conv1dWFn> {
         ctx->saved_data["has_bias"] = bias.has_value();
         ctx->saved_data["has_res"] = residual.has_value();
         ctx->saved_data["has_alpha"] = alpha.has_value();
+        ctx->saved_data["transposed"] = transposed;
+        if (transposed)
+            return conv_transpose1d_w_op(x, weight, packed, bias, alpha, residual, c_out, kernel, stride, act, slope,
+                                         precision);
         return conv1d_w_op(x, weight, packed, bias, alpha, residual, c_out, kernel, stride, dilation, pad_left, pad_right,
                            act, slope, precision);
     }
     static torch::autograd::variable_list backward(torch::autograd::AutogradContext* ctx,
                                                    torch::autograd::variable_list grads) {
-        no_double_backward("conv1d_w");
+        const bool transposed = ctx->saved_data["transposed"].toBool();
+        no_double_backward(transposed ? "conv_transpose1d_w" : "conv1d_w");
         at::AutoDispatchBelowADInplaceOrView below;
         const auto saved = ctx->get_saved_variables();
         c10::optional<at::Tensor> alpha;
@@ -738,13 +782,14 @@ struct Conv1dWFn : torch::autograd::Function<Conv1dWFn> {
                              (alpha.has_value() && ctx->needs_input_grad(e_alpha) ? 8 : 0);
         at::Tensor gy = grads[0].contiguous();
         auto opt = [](const at::Tensor& t) { return t.defined() ? c10::optional<at::Tensor>(t) : c10::nullopt; };
-        auto g = conv1d_backward_op(gy, opt(saved[0]), opt(saved[1]), alpha, ctx->saved_data["c_in"].toInt(),
+        auto g = conv_backward_impl(gy, opt(saved[0]), opt(saved[1]), alpha, ctx->saved_data["c_in"].toInt(),
                                     ctx->saved_data["t_in"].toInt(), ctx->saved_data["kernel"].toInt(),
                                     ctx->saved_data["stride"].toInt(), ctx->saved_data["dilation"].toInt(),
                                     ctx->saved_data["pad_left"].toInt(), ctx->saved_data["pad_right"].toInt(),
-                                    ctx->saved_data["act"].toInt(), ctx->saved_data["slope"].toDouble(), need);
+                                    ctx->saved_data["act"].toInt(), ctx->saved_data["slope"].toDouble(), need,
+                                    transposed);
         auto get = [](const c10::optional<at::Tensor>& t) { return t.has_value() ? *t : at::Tensor(); };
-        torch::autograd::variable_list out(15);
+        torch::autograd::variable_list out(16);
         out[0] = get(std::get<0>(g));
         out[1] = get(std::get<1>(g));
         out[3] = get(std::get<2>(g));
@@ -766,11 +811,28 @@ at::Tensor conv1d_w_autograd(at::Tensor x, at::Tensor weight, at::Tensor packed,
                                     precision, " with an input that requires grad");
         seam_tensor(x, "x");
         return Conv1dWFn::apply(x, weight, packed, bias, alpha, residual, c_out, kernel, stride, dilation, pad_left,
-                                pad_right, act, slope, precision);
+                                pad_right, act, slope, precision, false);
     }
     at::AutoDispatchBelowADInplaceOrView below;
     return conv1d_w_op(x, weight, packed, bias, alpha, residual, c_out, kernel, stride, dilation, pad_left, pad_right, act,
                        slope, precision);
+}
+
+at::Tensor conv_transpose1d_w_autograd(at::Tensor x, at::Tensor weight, at::Tensor packed, c10::optional<at::Tensor> bias,
+                                       c10::optional<at::Tensor> alpha, c10::optional<at::Tensor> residual, int64_t c_out,
+                                       int64_t kernel, int64_t stride, int64_t act, double slope, int64_t precision) {
+    auto rg = [](const c10::optional<at::Tensor>& t) { return t.has_value() && t->requires_grad(); };
+    const bool any = x.requires_grad() || weight.requires_grad() || rg(bias) || rg(alpha) || rg(residual);
+    if (at::GradMode::is_enabled() && any) {
+        TORCH_CHECK_NOT_IMPLEMENTED(precision == RAVE_PREC_F32,
+                                    "conv_transpose1d_w: only the exact fp32 precision (0) is differentiable; got "
+                                    "precision ", precision, " with an input that requires grad");
+        seam_tensor(x, "x");
+        return Conv1dWFn::apply(x, weight, packed, bias, alpha, residual, c_out, kernel, stride, 1, 0, 0, act, slope,
+                                precision, true);
+    }
+    at::AutoDispatchBelowADInplaceOrView below;
+    return conv_transpose1d_w_op(x, weight, packed, bias, alpha, residual, c_out, kernel, stride, act, slope, precision);
 }
 
 // rave_amd::adain -- AdaptiveInstanceNormalization.forward in eval mode
@@ -930,6 +992,11 @@ TORCH_LIBRARY(rave_amd, lib) {
             "int stride, int dilation, "
             "int pad_left, int pad_right, int act, float slope, int need) -> (Tensor? gx, Tensor? gweight, "
             "Tensor? gbias, Tensor? galpha)", &conv1d_backward_op);
+    lib.def("conv_transpose1d_w(Tensor x, Tensor weight, Tensor packed, Tensor? bias, Tensor? alpha, Tensor? residual, "
+            "int c_out, int kernel, int stride, int act, float slope, int precision) -> Tensor", &conv_transpose1d_w_op);
+    lib.def("conv_transpose1d_backward(Tensor gy, Tensor? x, Tensor? weight, Tensor? alpha, int c_in, int t_in, "
+            "int kernel, int stride, int act, float slope, int need) -> (Tensor? gx, Tensor? gweight, Tensor? gbias, "
+            "Tensor? galpha)", &conv_transpose1d_backward_op);
     lib.def("pqmf_analysis(Tensor x, Tensor hkf, int n_out_bands, int pad_left, int precision) -> Tensor",
             &pqmf_analysis_op);
     lib.def("pqmf_synthesis(Tensor x, Tensor hki, int pad_left, int frames, int frame0, int precision, int mode=0, "
@@ -986,4 +1053,5 @@ TORCH_LIBRARY_IMPL(rave_amd, AutogradCUDA, m) {
     m.impl("pqmf_analysis", &pqmf_analysis_autograd);
     m.impl("pqmf_synthesis", &pqmf_synthesis_autograd);
     m.impl("conv1d_w", &conv1d_w_autograd);
+    m.impl("conv_transpose1d_w", &conv_transpose1d_w_autograd);
 }
