@@ -1,6 +1,10 @@
 // Backward of rave_conv1d (gfx950), exact fp32 only: the data gradient, the
 // weight / bias gradient and Snake's alpha gradient, of the non-transposed conv
-// (first) and of the offline ConvTranspose1d (its own section below).
+// and of the offline ConvTranspose1d.  The families share the split-K slab
+// layout, the slab and alpha reduce kernels and the host side.  The two data kernels keep an epilogue each, word for word the
+// same but for the time index (t = u s + p against t = u): the transposed one at
+// r = 4 sits on the 256-register limit, where its speed follows any change of its
+// text, so folding the two waits for that kernel's staging batch to shrink.
 //
 // With a = act(x), zero outside [0, t_in), and the forward
 //   y[b, m, n] = bias[m] + sum_{ci, j} W[m, ci, j] a[b, ci, n s + j d - pl]  (+ res[b, m, n])
@@ -56,6 +60,37 @@ __device__ __forceinline__ void snake_parts(float z, float& sin2, float& ssq) {
     const float p2 = 2.0f * s * c;
     sin2 = odd ? -p2 : p2;
     ssq = odd ? c * c : s * s;
+}
+
+// ---------------------------------------------------------------- what the two families share
+// galpha[ci] = the partial rows in row order: one wave per ci, lane l takes rows
+// l, l + 64, ... in order, then a fixed butterfly.
+__global__ __launch_bounds__(64) void conv1d_grad_alpha_reduce_kernel(CgArgs a) {
+    const int ci = blockIdx.x, lane = threadIdx.x;
+    float v = 0.f;
+    for (int r = lane; r < a.P; r += 64) v += a.apart[(int64_t)r * a.c_in + ci];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    if (lane == 0) a.galpha[ci] = v;
+}
+
+// Split-K of the weight kernels: one slab layout for both families.  A slab is gweight in torch's
+// own layout (c_in c_out k floats, whichever channel leads), then c_out bias sums; a kernel stores
+// through dst = unsplit ? gweight : slab with one index, and a slab's weights only when gweight is
+// asked for.
+// Sum the slabs in slab order into gweight and gbias; an output not asked for is not read.
+__global__ __launch_bounds__(256) void grad_slab_reduce_kernel(CgArgs a) {
+    const int64_t WN = (int64_t)a.c_in * a.c_out * a.k, total = WN + a.c_out;
+    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const bool bias = i >= WN;
+        if (bias ? a.gb == nullptr : a.gw == nullptr) continue;
+        float v = 0.f;
+        for (int s = 0; s < a.S; ++s) v += a.slabs[(int64_t)s * total + i];
+        if (bias)
+            a.gb[i - WN] = v;
+        else
+            a.gw[i] = v;
+    }
 }
 
 // ---------------------------------------------------------------- data gradient
@@ -188,17 +223,6 @@ __global__ __launch_bounds__(256) void conv1d_grad_data_kernel(CgArgs a) {
     }
 }
 
-// galpha[ci] = the partial rows in row order: one wave per ci, lane l takes rows
-// l, l + 64, ... in order, then a fixed butterfly.
-__global__ __launch_bounds__(64) void conv1d_grad_alpha_reduce_kernel(CgArgs a) {
-    const int ci = blockIdx.x, lane = threadIdx.x;
-    float v = 0.f;
-    for (int r = lane; r < a.P; r += 64) v += a.apart[(int64_t)r * a.c_in + ci];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    if (lane == 0) a.galpha[ci] = v;
-}
-
 // ---------------------------------------------------------------- weight gradient
 constexpr int kWgMT = 64;          // rows m per workgroup: one MFMA row block per wave
 constexpr int kWgCT = 16;          // input channels per workgroup: one column block per tap
@@ -289,53 +313,28 @@ __global__ __launch_bounds__(256) void conv1d_grad_weight_kernel(CgArgs a) {
         }
     }
     // D: row m = 4 kk + r of this wave's row block, column ci = col
-    const int NW = a.c_in * KT + 1;                       // slab row: c_in x k weights, then the bias
+    const int64_t WN = (int64_t)a.c_in * a.c_out * KT;    // slab: the weights, then c_out bias sums
     const bool direct = a.S == 1;
-    float* slab = direct ? nullptr : a.slabs + (int64_t)sp * a.c_out * NW;
+    float* dst = direct ? a.gw : a.slabs + (int64_t)sp * (WN + a.c_out);
     const int ci = ci0 + col;
-    if (ci < a.c_in && (a.gw || !direct)) {
+    if (a.gw && ci < a.c_in) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int m = m0 + wave * 16 + 4 * kk + r;
             if (m >= a.c_out) continue;
 #pragma unroll
-            for (int j = 0; j < KT; ++j) {
-                if (direct)
-                    a.gw[((int64_t)m * a.c_in + ci) * KT + j] = acc[j][r];
-                else
-                    slab[(int64_t)m * NW + ci * KT + j] = acc[j][r];
-            }
+            for (int j = 0; j < KT; ++j) dst[((int64_t)m * a.c_in + ci) * KT + j] = acc[j][r];
         }
     }
     // gbias: this lane's A values are row `col`, k = kk: sum the four k lanes
     bsum += __shfl_xor(bsum, 16);
     bsum += __shfl_xor(bsum, 32);
-    if (blockIdx.y == 0 && lane < 16) {
-        const int m = m0 + wave * 16 + lane;
-        if (m < a.c_out) {
-            if (!direct)
-                slab[(int64_t)m * NW + NW - 1] = bsum;
-            else if (a.gb)
-                a.gb[m] = bsum;
-        }
-    }
-}
-
-// Sum the slabs in slab order into gweight (torch layout) and gbias.
-__global__ __launch_bounds__(256) void conv1d_grad_weight_reduce_kernel(CgArgs a) {
-    const int NW = a.c_in * a.k + 1;
-    const int64_t total = (int64_t)a.c_out * NW;
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-        const int m = (int)(i / NW);
-        const int c = (int)(i - (int64_t)m * NW);
-        const bool bias = c == NW - 1;
-        if (bias ? a.gb == nullptr : a.gw == nullptr) continue;
-        float v = 0.f;
-        for (int s = 0; s < a.S; ++s) v += a.slabs[(int64_t)s * total + i];
-        if (bias)
-            a.gb[m] = v;
-        else
-            a.gw[(int64_t)m * (NW - 1) + c] = v;
+    const int m = m0 + wave * 16 + lane;
+    if (blockIdx.y == 0 && lane < 16 && m < a.c_out) {
+        if (!direct)
+            dst[WN + m] = bsum;
+        else if (a.gb)
+            a.gb[m] = bsum;
     }
 }
 
@@ -344,9 +343,10 @@ __global__ __launch_bounds__(256) void conv1d_grad_weight_reduce_kernel(CgArgs a
 // W in torch's layout (c_in, c_out, 2 r), P = r/2:
 //   ga[b, ci, u]  = sum_{m, j} W[ci, m, j] gy[b, m, u r + j - P]           gx = ga act'(x)
 //   gW[ci, m, j]  = sum_{b, u} a[b, ci, u] gy[b, m, u r + j - P]           gbias[m] = sum_{b, t} gy[b, m, t]
-// Both kernels stage their gy window de-interleaved by phase: window column w (t = (u0 - 1) r + w)
-// sits at [m][w mod r][w / r], so tap j of column u is phase q(j) = (j + r/2) mod r at index
-// (u - u0) + sh(j), sh(j) = (j + r/2) / r in {0, 1, 2}: a fragment walks u at stride 1.
+// Both kernels stage their gy window de-interleaved by phase: window column w
+// (t = (u0 - 1) r + w) sits at [m][w mod r][w / r], so tap j of column u is phase
+// q(j) = (j + r/2) mod r at index (u - u0) + sh(j), sh(j) = (j + r/2) / r in {0, 1, 2}: a
+// fragment walks u at stride 1.
 //
 // data:   rows ci, columns u, K = (m, j) with the four k of an MFMA four taps of one m: the A
 //         fragment is then four consecutive floats of W's own row, and the weight chunk is a
@@ -606,26 +606,13 @@ __global__ __launch_bounds__(256) void convt1d_grad_weight_kernel(CgArgs a) {
     }
 }
 
-// Sum the slabs in slab order into gweight (torch layout (c_in, c_out, 2 r)) and gbias.
-__global__ __launch_bounds__(256) void convt1d_grad_weight_reduce_kernel(CgArgs a) {
-    const int64_t WN = (int64_t)a.c_in * a.c_out * a.k, total = WN + a.c_out;
-    for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
-        const bool bias = i >= WN;
-        if (bias ? a.gb == nullptr : a.gw == nullptr) continue;
-        float v = 0.f;
-        for (int s = 0; s < a.S; ++s) v += a.slabs[(int64_t)s * total + i];
-        if (bias)
-            a.gb[i - WN] = v;
-        else
-            a.gw[i] = v;
-    }
-}
-
 // ---------------------------------------------------------------- host side
+using BwdArgs = rave_conv1d_backward_args;
+
 // The forward's refusals (conv_shared.h prepare_common) in its order, then this file's own.
-static int check_args(const rave_conv1d_backward_args* p) {
+static int check_args(const BwdArgs* p) {
     RAVE_CHECK_ARG(p, "conv1d_backward: null args");
-    const rave_conv1d_backward_args& a = *p;
+    const BwdArgs& a = *p;
     RAVE_CHECK_ARG(a.precision == RAVE_PREC_F32, "conv1d_backward: precision must be RAVE_PREC_F32");
     RAVE_CHECK_ARG(a.batch > 0 && a.t_in > 0 && a.t_out > 0 && a.c_in > 0 && a.c_out > 0,
                    "conv1d_backward: empty shape");
@@ -645,50 +632,10 @@ static int check_args(const rave_conv1d_backward_args* p) {
     return RAVE_OK;
 }
 
-struct WgSplit {
-    int S, cps, nch, tch;
-};
-static WgSplit weight_split(const rave_conv1d_backward_args& a) {
-    WgSplit w;
-    w.tch = ceil_div(a.t_out, kWgTK);
-    w.nch = a.batch * w.tch;
-    const int tiles = ceil_div(a.c_out, kWgMT) * ceil_div(a.c_in, kWgCT);
-    // fill two workgroups per CU, each split at least four chunks (256 columns) long
-    int S = std::max(1, std::min(ceil_div(512, tiles), w.nch / 4));
-    w.cps = ceil_div(w.nch, S);
-    w.S = ceil_div(w.nch, w.cps);
-    return w;
-}
-static inline int64_t slab_floats(const rave_conv1d_backward_args& a) {
-    if (!a.gweight && !a.gbias) return 0;
-    const WgSplit w = weight_split(a);
-    return w.S > 1 ? (int64_t)w.S * a.c_out * ((int64_t)a.c_in * a.kernel + 1) : 0;
-}
-static inline dim3 data_grid(const rave_conv1d_backward_args& a) {
-    return dim3(ceil_div(ceil_div(a.t_in, a.stride), kDgTN), ceil_div(a.c_in, kDgCT), a.batch * a.stride);
-}
-static inline int64_t alpha_floats(const rave_conv1d_backward_args& a) {
-    if (a.act != RAVE_ACT_SNAKE || !a.galpha) return 0;
-    const dim3 g = data_grid(a);
-    return (int64_t)g.x * g.z * a.c_in;
-}
-
-static CgArgs kernel_args(const rave_conv1d_backward_args& a) {
-    CgArgs k{};
-    k.x = a.x; k.gy = a.gy; k.w = a.weight; k.alpha = a.alpha;
-    k.gx = a.gx; k.gw = a.gweight; k.gb = a.gbias; k.galpha = a.galpha;
-    k.x_sb = a.x_sb; k.x_sc = a.x_sc; k.gy_sb = a.gy_sb; k.gy_sc = a.gy_sc; k.gx_sb = a.gx_sb; k.gx_sc = a.gx_sc;
-    k.c_in = a.c_in; k.c_out = a.c_out; k.k = a.kernel; k.s = a.stride; k.d = a.dilation; k.pl = a.pad_left;
-    k.t_in = a.t_in; k.t_out = a.t_out; k.B = a.batch; k.act = a.act; k.slope = a.leaky_slope;
-    k.slabs = a.workspace;
-    k.apart = a.workspace ? a.workspace + slab_floats(a) : nullptr;
-    return k;
-}
-
-// ---- transposed: the offline geometry only, strides 2 and 4
-static int check_args_t(const rave_conv1d_backward_args* p) {
+// transposed: the offline geometry only, strides 2 and 4
+static int check_args_t(const BwdArgs* p) {
     RAVE_CHECK_ARG(p, "conv_transpose1d_backward: null args");
-    const rave_conv1d_backward_args& a = *p;
+    const BwdArgs& a = *p;
     RAVE_CHECK_ARG(a.precision == RAVE_PREC_F32, "conv_transpose1d_backward: precision must be RAVE_PREC_F32");
     RAVE_CHECK_ARG(a.transposed == 1, "conv_transpose1d_backward: transposed must be 1 (rave_conv1d_backward_* takes the rest)");
     RAVE_CHECK_ARG(a.batch > 0 && a.t_in > 0 && a.t_out > 0 && a.c_in > 0 && a.c_out > 0,
@@ -707,148 +654,178 @@ static int check_args_t(const rave_conv1d_backward_args* p) {
     return RAVE_OK;
 }
 
-static WgSplit weight_split_t(const rave_conv1d_backward_args& a) {
+struct WgSplit {
+    int S, cps, nch, tch;
+};
+// (the same split with and without gweight: gbias keeps its bits)  fill two workgroups per CU,
+// each split at least four chunks (256 columns of K) long
+static WgSplit weight_split(int chunks_per_row, int batch, int tiles) {
     WgSplit w;
-    w.tch = ceil_div(a.t_in, kTwTK);
-    w.nch = a.batch * w.tch;
-    const int tiles = ceil_div(a.c_in, kTwCT) * ceil_div(a.c_out, kTwMT);
-    // (the same split with and without gweight: gbias keeps its bits)  fill two workgroups per CU, each split at least four chunks (256 input columns) long
-    int S = std::max(1, std::min(ceil_div(512, tiles), w.nch / 4));
+    w.tch = chunks_per_row;
+    w.nch = batch * w.tch;
+    const int S = std::max(1, std::min(ceil_div(512, tiles), w.nch / 4));
     w.cps = ceil_div(w.nch, S);
     w.S = ceil_div(w.nch, w.cps);
     return w;
 }
-static inline int64_t slab_floats_t(const rave_conv1d_backward_args& a) {
-    if (!a.gweight && !a.gbias) return 0;
-    const WgSplit w = weight_split_t(a);
-    return w.S > 1 ? (int64_t)w.S * ((int64_t)a.c_in * a.c_out * a.kernel + a.c_out) : 0;
+
+enum CgFamily { kFamConv, kFamConvT };
+
+// A family's launches and workspace for one call.  A new family adds its name here, its checker, a
+// function that fills name, data_z, the grids' x and y and the split from its tile constants, and
+// its cases to the switches of make_plan, backward_data and backward_weight.
+struct CgPlan {
+    const char* name;             // the messages' prefix
+    dim3 data_grid, weight_grid;  // data_grid.z is set from data_z once that is known to fit
+    int64_t data_z;
+    WgSplit split;
+    int64_t slab_floats, alpha_floats;                    // the workspace: weight slabs, then alpha partial rows
+};
+
+static void plan_conv(const BwdArgs& a, CgPlan& pl) {
+    pl.name = "conv1d_backward";
+    pl.data_grid = dim3(ceil_div(ceil_div(a.t_in, a.stride), kDgTN), ceil_div(a.c_in, kDgCT));
+    pl.data_z = (int64_t)a.batch * a.stride;
+    const int mt = ceil_div(a.c_out, kWgMT), ct = ceil_div(a.c_in, kWgCT);
+    pl.split = weight_split(ceil_div(a.t_out, kWgTK), a.batch, mt * ct);
+    // bias only: one ci tile carries the row sums (x is not read, no weight is stored)
+    pl.weight_grid = dim3(mt, a.gweight ? ct : 1);
 }
-static inline dim3 data_grid_t(const rave_conv1d_backward_args& a) {
-    return dim3(ceil_div(a.t_in, kTdTN), ceil_div(a.c_in, kTdCT), a.batch);
+
+static void plan_convt(const BwdArgs& a, CgPlan& pl) {
+    pl.name = "conv_transpose1d_backward";
+    pl.data_grid = dim3(ceil_div(a.t_in, kTdTN), ceil_div(a.c_in, kTdCT));
+    pl.data_z = a.batch;
+    const int ct = ceil_div(a.c_in, kTwCT), mt = ceil_div(a.c_out, kTwMT);
+    pl.split = weight_split(ceil_div(a.t_in, kTwTK), a.batch, ct * mt);
+    // bias only: one ci tile carries the column sums (x is not read, no weight is stored)
+    pl.weight_grid = dim3(a.gweight ? ct : 1, mt);
 }
-static inline int64_t alpha_floats_t(const rave_conv1d_backward_args& a) {
-    if (a.act != RAVE_ACT_SNAKE || !a.galpha) return 0;
-    const dim3 g = data_grid_t(a);
-    return (int64_t)g.x * g.z * a.c_in;
+
+static int make_plan(const BwdArgs* p, CgFamily fam, CgPlan& pl) {
+    const int rc = fam == kFamConvT ? check_args_t(p) : check_args(p);
+    if (rc != RAVE_OK) return rc;
+    const BwdArgs& a = *p;
+    switch (fam) {
+        case kFamConv: plan_conv(a, pl); break;
+        case kFamConvT: plan_convt(a, pl); break;
+    }
+    pl.weight_grid.z = pl.split.S;
+    const bool slabs = (a.gweight || a.gbias) && pl.split.S > 1;
+    pl.slab_floats = slabs ? (int64_t)pl.split.S * ((int64_t)a.c_in * a.c_out * a.kernel + a.c_out) : 0;
+    const bool alpha = a.act == RAVE_ACT_SNAKE && a.galpha;
+    pl.alpha_floats = alpha ? (int64_t)pl.data_grid.x * pl.data_z * a.c_in : 0;
+    return RAVE_OK;
+}
+
+static CgArgs kernel_args(const BwdArgs& a, const CgPlan& pl) {
+    CgArgs k{};
+    k.x = a.x; k.gy = a.gy; k.w = a.weight; k.alpha = a.alpha;
+    k.gx = a.gx; k.gw = a.gweight; k.gb = a.gbias; k.galpha = a.galpha;
+    k.x_sb = a.x_sb; k.x_sc = a.x_sc; k.gy_sb = a.gy_sb; k.gy_sc = a.gy_sc; k.gx_sb = a.gx_sb; k.gx_sc = a.gx_sc;
+    k.c_in = a.c_in; k.c_out = a.c_out; k.k = a.kernel; k.s = a.stride; k.d = a.dilation; k.pl = a.pad_left;
+    k.t_in = a.t_in; k.t_out = a.t_out; k.B = a.batch; k.act = a.act; k.slope = a.leaky_slope;
+    k.slabs = a.workspace;
+    k.apart = pl.alpha_floats && a.workspace ? a.workspace + pl.slab_floats : nullptr;
+    k.S = pl.split.S; k.cps = pl.split.cps; k.nch = pl.split.nch; k.tch = pl.split.tch;
+    return k;
+}
+
+static int64_t backward_workspace(const BwdArgs* p, CgFamily fam) {
+    CgPlan pl;
+    const int rc = make_plan(p, fam, pl);
+    return rc != RAVE_OK ? rc : pl.slab_floats + pl.alpha_floats;
+}
+
+static int backward_data(const BwdArgs* p, void* stream, CgFamily fam) {
+    CgPlan pl;
+    const int rc = make_plan(p, fam, pl);
+    if (rc != RAVE_OK) return rc;
+    const BwdArgs& a = *p;
+    const bool want_alpha = pl.alpha_floats > 0;
+    if (!a.gx && !want_alpha) return RAVE_OK;
+    const auto msg = [&](const char* what) { return std::string(pl.name) + "_data: " + what; };
+    RAVE_CHECK_ARG(a.gy && a.weight, msg("null gy or weight"));
+    RAVE_CHECK_ARG(a.act == RAVE_ACT_NONE || a.x, msg("the activation's derivative needs the input x"));
+    RAVE_CHECK_ARG(!want_alpha || a.workspace, msg("galpha needs the workspace"));
+    RAVE_CHECK_ARG(pl.data_grid.y <= 65535 && pl.data_z <= 65535, msg("grid beyond 65535 in y or z"));
+    const dim3 grid(pl.data_grid.x, pl.data_grid.y, (unsigned)pl.data_z);
+    CgArgs k = kernel_args(a, pl);
+    k.P = (int)(grid.x * grid.z);
+    hipStream_t st = as_stream(stream);
+    const char* kernel = "conv1d_grad_data_kernel";
+    switch (fam) {
+        case kFamConv: launch(conv1d_grad_data_kernel, grid, dim3(256), 0, st, k); break;
+        case kFamConvT:
+            kernel = "convt1d_grad_data_kernel";
+            if (a.stride == 2)
+                launch(convt1d_grad_data_kernel<2>, grid, dim3(256), 0, st, k);
+            else
+                launch(convt1d_grad_data_kernel<4>, grid, dim3(256), 0, st, k);
+            break;
+    }
+    const int s = launch_status(kernel);
+    if (s != RAVE_OK || !want_alpha) return s;
+    launch(conv1d_grad_alpha_reduce_kernel, dim3(a.c_in), dim3(64), 0, st, k);
+    return launch_status("conv1d_grad_alpha_reduce_kernel");
+}
+
+static int backward_weight(const BwdArgs* p, void* stream, CgFamily fam) {
+    CgPlan pl;
+    const int rc = make_plan(p, fam, pl);
+    if (rc != RAVE_OK) return rc;
+    const BwdArgs& a = *p;
+    if (!a.gweight && !a.gbias) return RAVE_OK;
+    const auto msg = [&](const char* what) { return std::string(pl.name) + "_weight: " + what; };
+    RAVE_CHECK_ARG(a.gy, msg("null gy"));
+    RAVE_CHECK_ARG(a.x || !a.gweight, msg("gweight needs the input x"));
+    RAVE_CHECK_ARG(pl.split.S == 1 || a.workspace, msg("the K split needs the workspace"));
+    const dim3 grid = pl.weight_grid;
+    RAVE_CHECK_ARG(grid.y <= 65535 && grid.z <= 65535, msg("grid beyond 65535 in y or z"));
+    const CgArgs k = kernel_args(a, pl);
+    hipStream_t st = as_stream(stream);
+    const char* kernel = "conv1d_grad_weight_kernel";
+    switch (fam) {
+        case kFamConv:
+            switch (a.kernel) {
+                case 1: launch(conv1d_grad_weight_kernel<1>, grid, dim3(256), 0, st, k); break;
+                case 3: launch(conv1d_grad_weight_kernel<3>, grid, dim3(256), 0, st, k); break;
+                case 7: launch(conv1d_grad_weight_kernel<7>, grid, dim3(256), 0, st, k); break;
+                case 4: launch(conv1d_grad_weight_kernel<4>, grid, dim3(256), 0, st, k); break;
+                default: launch(conv1d_grad_weight_kernel<8>, grid, dim3(256), 0, st, k); break;
+            }
+            break;
+        case kFamConvT:
+            kernel = "convt1d_grad_weight_kernel";
+            if (a.stride == 2)
+                launch(convt1d_grad_weight_kernel<2>, grid, dim3(256), 0, st, k);
+            else
+                launch(convt1d_grad_weight_kernel<4>, grid, dim3(256), 0, st, k);
+            break;
+    }
+    const int s = launch_status(kernel);
+    if (s != RAVE_OK || pl.split.S == 1) return s;
+    const int64_t total = (int64_t)a.c_in * a.c_out * a.kernel + a.c_out;
+    const dim3 rgrid((unsigned)std::min<int64_t>(1024, ceil_div64(total, 256)));
+    launch(grad_slab_reduce_kernel, rgrid, dim3(256), 0, st, k);
+    return launch_status("grad_slab_reduce_kernel");
 }
 
 }  // namespace rave
 
 using namespace rave;
 
-extern "C" int64_t rave_conv_transpose1d_backward_workspace(const rave_conv1d_backward_args* p) {
-    const int rc = check_args_t(p);
-    if (rc != RAVE_OK) return rc;
-    return slab_floats_t(*p) + alpha_floats_t(*p);
+extern "C" int64_t rave_conv1d_backward_workspace(const BwdArgs* p) { return backward_workspace(p, kFamConv); }
+extern "C" int rave_conv1d_backward_data(const BwdArgs* p, void* stream) { return backward_data(p, stream, kFamConv); }
+extern "C" int rave_conv1d_backward_weight(const BwdArgs* p, void* stream) {
+    return backward_weight(p, stream, kFamConv);
 }
-
-extern "C" int rave_conv_transpose1d_backward_data(const rave_conv1d_backward_args* p, void* stream) {
-    const int rc = check_args_t(p);
-    if (rc != RAVE_OK) return rc;
-    const rave_conv1d_backward_args& a = *p;
-    const bool want_alpha = a.act == RAVE_ACT_SNAKE && a.galpha;
-    if (!a.gx && !want_alpha) return RAVE_OK;
-    RAVE_CHECK_ARG(a.gy && a.weight, "conv_transpose1d_backward_data: null gy or weight");
-    RAVE_CHECK_ARG(a.act == RAVE_ACT_NONE || a.x,
-                   "conv_transpose1d_backward_data: the activation's derivative needs the input x");
-    RAVE_CHECK_ARG(!want_alpha || a.workspace, "conv_transpose1d_backward_data: galpha needs the workspace");
-    const dim3 grid = data_grid_t(a);
-    RAVE_CHECK_ARG(grid.y <= 65535 && grid.z <= 65535, "conv_transpose1d_backward_data: grid beyond 65535 in y or z");
-    CgArgs k = kernel_args(a);
-    k.apart = want_alpha ? a.workspace + slab_floats_t(a) : nullptr;
-    k.P = (int)(grid.x * grid.z);
-    if (a.stride == 2)
-        launch(convt1d_grad_data_kernel<2>, grid, dim3(256), 0, as_stream(stream), k);
-    else
-        launch(convt1d_grad_data_kernel<4>, grid, dim3(256), 0, as_stream(stream), k);
-    int st = launch_status("convt1d_grad_data_kernel");
-    if (st != RAVE_OK || !want_alpha) return st;
-    launch(conv1d_grad_alpha_reduce_kernel, dim3(a.c_in), dim3(64), 0, as_stream(stream), k);
-    return launch_status("conv1d_grad_alpha_reduce_kernel");
+extern "C" int64_t rave_conv_transpose1d_backward_workspace(const BwdArgs* p) {
+    return backward_workspace(p, kFamConvT);
 }
-
-extern "C" int rave_conv_transpose1d_backward_weight(const rave_conv1d_backward_args* p, void* stream) {
-    const int rc = check_args_t(p);
-    if (rc != RAVE_OK) return rc;
-    const rave_conv1d_backward_args& a = *p;
-    if (!a.gweight && !a.gbias) return RAVE_OK;
-    RAVE_CHECK_ARG(a.gy, "conv_transpose1d_backward_weight: null gy");
-    RAVE_CHECK_ARG(a.x || !a.gweight, "conv_transpose1d_backward_weight: gweight needs the input x");
-    const WgSplit w = weight_split_t(a);
-    RAVE_CHECK_ARG(w.S == 1 || a.workspace, "conv_transpose1d_backward_weight: the K split needs the workspace");
-    CgArgs k = kernel_args(a);
-    k.S = w.S; k.cps = w.cps; k.nch = w.nch; k.tch = w.tch;
-    // bias only: one ci tile carries the column sums (x is not read, no weight is stored)
-    const dim3 grid(a.gweight ? ceil_div(a.c_in, kTwCT) : 1, ceil_div(a.c_out, kTwMT), w.S);
-    RAVE_CHECK_ARG(grid.y <= 65535 && grid.z <= 65535,
-                   "conv_transpose1d_backward_weight: grid beyond 65535 in y or z");
-    hipStream_t st = as_stream(stream);
-    if (a.stride == 2)
-        launch(convt1d_grad_weight_kernel<2>, grid, dim3(256), 0, st, k);
-    else
-        launch(convt1d_grad_weight_kernel<4>, grid, dim3(256), 0, st, k);
-    int s = launch_status("convt1d_grad_weight_kernel");
-    if (s != RAVE_OK || w.S == 1) return s;
-    const int64_t total = (int64_t)a.c_in * a.c_out * a.kernel + a.c_out;
-    launch(convt1d_grad_weight_reduce_kernel, dim3((unsigned)std::min<int64_t>(1024, ceil_div64(total, 256))), dim3(256),
-           0, st, k);
-    return launch_status("convt1d_grad_weight_reduce_kernel");
+extern "C" int rave_conv_transpose1d_backward_data(const BwdArgs* p, void* stream) {
+    return backward_data(p, stream, kFamConvT);
 }
-
-extern "C" int64_t rave_conv1d_backward_workspace(const rave_conv1d_backward_args* p) {
-    const int rc = check_args(p);
-    if (rc != RAVE_OK) return rc;
-    return slab_floats(*p) + alpha_floats(*p);
-}
-
-extern "C" int rave_conv1d_backward_data(const rave_conv1d_backward_args* p, void* stream) {
-    const int rc = check_args(p);
-    if (rc != RAVE_OK) return rc;
-    const rave_conv1d_backward_args& a = *p;
-    const bool want_alpha = a.act == RAVE_ACT_SNAKE && a.galpha;
-    if (!a.gx && !want_alpha) return RAVE_OK;
-    RAVE_CHECK_ARG(a.gy && a.weight, "conv1d_backward_data: null gy or weight");
-    RAVE_CHECK_ARG(a.act == RAVE_ACT_NONE || a.x, "conv1d_backward_data: the activation's derivative needs the input x");
-    RAVE_CHECK_ARG(!want_alpha || a.workspace, "conv1d_backward_data: galpha needs the workspace");
-    RAVE_CHECK_ARG((int64_t)a.batch * a.stride <= 65535 && ceil_div(a.c_in, kDgCT) <= 65535,
-                   "conv1d_backward_data: grid beyond 65535 in y or z");
-    CgArgs k = kernel_args(a);
-    if (!want_alpha) k.apart = nullptr;
-    const dim3 grid = data_grid(a);
-    k.P = (int)(grid.x * grid.z);
-    launch(conv1d_grad_data_kernel, grid, dim3(256), 0, as_stream(stream), k);
-    int st = launch_status("conv1d_grad_data_kernel");
-    if (st != RAVE_OK || !want_alpha) return st;
-    launch(conv1d_grad_alpha_reduce_kernel, dim3(a.c_in), dim3(64), 0, as_stream(stream), k);
-    return launch_status("conv1d_grad_alpha_reduce_kernel");
-}
-
-extern "C" int rave_conv1d_backward_weight(const rave_conv1d_backward_args* p, void* stream) {
-    const int rc = check_args(p);
-    if (rc != RAVE_OK) return rc;
-    const rave_conv1d_backward_args& a = *p;
-    if (!a.gweight && !a.gbias) return RAVE_OK;
-    RAVE_CHECK_ARG(a.gy, "conv1d_backward_weight: null gy");
-    RAVE_CHECK_ARG(a.x || !a.gweight, "conv1d_backward_weight: gweight needs the input x");
-    const WgSplit w = weight_split(a);
-    RAVE_CHECK_ARG(w.S == 1 || a.workspace, "conv1d_backward_weight: the K split needs the workspace");
-    CgArgs k = kernel_args(a);
-    k.S = w.S; k.cps = w.cps; k.nch = w.nch; k.tch = w.tch;
-    // bias only: one ci tile carries the row sums (its weight columns are not stored / not summed)
-    const dim3 grid(ceil_div(a.c_out, kWgMT), a.gweight ? ceil_div(a.c_in, kWgCT) : 1, w.S);
-    RAVE_CHECK_ARG(grid.y <= 65535 && grid.z <= 65535, "conv1d_backward_weight: grid beyond 65535 in y or z");
-    hipStream_t st = as_stream(stream);
-    switch (a.kernel) {
-        case 1: launch(conv1d_grad_weight_kernel<1>, grid, dim3(256), 0, st, k); break;
-        case 3: launch(conv1d_grad_weight_kernel<3>, grid, dim3(256), 0, st, k); break;
-        case 7: launch(conv1d_grad_weight_kernel<7>, grid, dim3(256), 0, st, k); break;
-        case 4: launch(conv1d_grad_weight_kernel<4>, grid, dim3(256), 0, st, k); break;
-        default: launch(conv1d_grad_weight_kernel<8>, grid, dim3(256), 0, st, k); break;
-    }
-    int s = launch_status("conv1d_grad_weight_kernel");
-    if (s != RAVE_OK || w.S == 1) return s;
-    const int64_t total = (int64_t)a.c_out * ((int64_t)a.c_in * a.kernel + 1);
-    launch(conv1d_grad_weight_reduce_kernel, dim3((unsigned)std::min<int64_t>(1024, ceil_div64(total, 256))), dim3(256), 0,
-           st, k);
-    return launch_status("conv1d_grad_weight_reduce_kernel");
+extern "C" int rave_conv_transpose1d_backward_weight(const BwdArgs* p, void* stream) {
+    return backward_weight(p, stream, kFamConvT);
 }

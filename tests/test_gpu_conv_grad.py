@@ -15,8 +15,9 @@ import numpy as np
 import pytest
 import torch
 
-from tests import conv_grad_ref as G
-from tests.test_gpu_aux_kernels import DEV, maxerr, put, guarded, report, same_bits, untouched
+from tests import conv_grad_harness as H, conv_grad_ref as G
+from tests.conv_grad_harness import native as _N
+from tests.test_gpu_aux_kernels import DEV, same_bits
 
 pytestmark = pytest.mark.gpu
 T_OUTS = [1, 2, 31, 32, 33, 63, 64, 65, 129, 257]
@@ -24,15 +25,6 @@ T_OUTS = [1, 2, 31, 32, 33, 63, 64, 65, 129, 257]
 # last (small) ones go with the long t_out so that the reference's Python loops stay short
 PAIRS = [(16, 16), (40, 16), (16, 40), (64, 40), (40, 64), (136, 16), (16, 136), (64, 64), (40, 40), (16, 64)]
 ACTS = [G.ACT_NONE, G.ACT_LEAKY, G.ACT_SNAKE]
-
-
-def _N():
-    from rave_amd import _native as N
-    return N
-
-
-def _st():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def _geometry(fam, pad, t_out):
@@ -68,59 +60,9 @@ def _args(c, **kw):
     return a
 
 
-def _bwd(c, want=("gx", "gw", "gb", "ga"), null_x=False, check=True, **kw):
+def _bwd(c, **kw):
     """One data + one weight call on guarded views; returns (dict of outputs, workspace floats)."""
-    N = _N()
-    B, ci, co = c["B"], c["c_in"], c["c_out"]
-    xb, xv, xm = put(c["x"], [(1, 1), (2, 3), (5, 7)])
-    gb_, gv, gm = put(c["gy"], [(0, 1), (3, 1), (4, 9)])
-    ob, ov, om = guarded((B, ci, c["t_in"]), [(1, 0), (1, 2), (8, 3)])
-    w = torch.from_numpy(c["w"]).to(DEV)
-    al = torch.from_numpy(c["alpha"]).to(DEV)
-    gw = torch.full((co * ci * c["k"] + 16,), float("nan"), device=DEV)
-    gbias = torch.full((co + 16,), float("nan"), device=DEV)
-    galpha = torch.full((ci + 16,), float("nan"), device=DEV)
-    a = _args(c, **kw)
-    if not null_x:
-        a.x, a.x_sb, a.x_sc = xv.data_ptr(), xv.stride(0), xv.stride(1)
-    a.gy, a.gy_sb, a.gy_sc = gv.data_ptr(), gv.stride(0), gv.stride(1)
-    a.weight = w.data_ptr()
-    if c["act"] == G.ACT_SNAKE:
-        a.alpha = al.data_ptr()
-    if "gx" in want:
-        a.gx, a.gx_sb, a.gx_sc = ov.data_ptr(), ov.stride(0), ov.stride(1)
-    if "gw" in want:
-        a.gweight = gw.data_ptr()
-    if "gb" in want:
-        a.gbias = gbias.data_ptr()
-    if "ga" in want and c["act"] == G.ACT_SNAKE:
-        a.galpha = galpha.data_ptr()
-    nws = N.lib.rave_conv1d_backward_workspace(C.byref(a))
-    if nws < 0:
-        return nws, None
-    ws = torch.full((max(nws, 1) + 16,), float("nan"), device=DEV)      # never zeroed
-    if nws > 0:
-        a.workspace = ws.data_ptr()
-    rc = N.lib.rave_conv1d_backward_data(C.byref(a), _st())
-    if rc == N.RAVE_OK:
-        rc = N.lib.rave_conv1d_backward_weight(C.byref(a), _st())
-    if not check:
-        return rc, None
-    N.check(rc)
-    torch.cuda.synchronize()
-    assert untouched(xb, xm) and untouched(gb_, gm) and untouched(ob, om)
-    assert bool(torch.isnan(gw[co * ci * c["k"]:]).all() and torch.isnan(gbias[co:]).all() and torch.isnan(galpha[ci:]).all())
-    assert bool(torch.isnan(ws[max(nws, 1):]).all())
-    out = {}
-    if "gx" in want:
-        out["gx"] = ov.clone()
-    if "gw" in want:
-        out["gw"] = gw[:co * ci * c["k"]].reshape(co, ci, c["k"]).clone()
-    if "gb" in want:
-        out["gb"] = gbias[:co].clone()
-    if "ga" in want and c["act"] == G.ACT_SNAKE:
-        out["ga"] = galpha[:ci].clone()
-    return out, nws
+    return H.bwd("rave_conv1d_backward", (c["c_out"], c["c_in"], c["k"]), _args, c, **kw)
 
 
 def _ref(c):
@@ -129,18 +71,7 @@ def _ref(c):
 
 def _held(what, out, c):
     """Print every figure, then assert 4 e_ref per output; returns the worst ratio."""
-    r64, e = _ref(c)
-    worst, fails = 0.0, []
-    for name, ref, e_ref in zip(("gx", "gw", "gb", "ga"), r64, e):
-        if ref is None or name not in out:
-            continue
-        err = maxerr(out[name], ref)
-        worst = max(worst, report(f"{what} {name}", err, e_ref))
-        assert bool(torch.isfinite(out[name]).all()), (what, name)
-        if err > 4 * e_ref:
-            fails.append((name, err, e_ref))
-    assert not fails, (what, fails)
-    return worst
+    return H.held(what, out, _ref(c))
 
 
 # ================================================================== 1. the edge sweep
