@@ -176,6 +176,18 @@ int64_t rave_conv1d_packed_size(int c_in, int c_out, int kernel, int stride, int
  * ConvTranspose1d: (c_in, c_out, k)) into the kernel's K-chunked layout. */
 int rave_conv1d_pack_weight(const float* w, int c_in, int c_out, int kernel, int stride,
                             int dilation, int transposed, int out_shift, float* packed);
+/* The same image made on the device (exact fp32 only): `w` and `packed` are
+ * device pointers, and the copy is one kernel launch on `stream`, with no
+ * allocation and no host synchronisation, so a host that updates its weights on
+ * the GPU (an optimiser step) never takes them through the CPU.  Every float of
+ * rave_conv1d_packed_size() is written, the padding rows and columns and the
+ * tail beyond this out_shift's row layout as zeros: `packed` needs no clearing.
+ * The bytes are rave_conv1d_pack_weight's into a zeroed buffer.  Refusals are
+ * the host packer's, in its order and with its status codes (messages prefixed
+ * "pack_weight_device:"), and are made before anything touches the GPU. */
+int rave_conv1d_pack_weight_device(const float* w, int c_in, int c_out, int kernel, int stride,
+                                   int dilation, int transposed, int out_shift, float* packed,
+                                   void* stream);
 /* Launch configurations (tile shape, K-splits, split-K combine) valid for
  * these args and precision, for plan-time autotuning (cf. cuDNN's Find API):
  * writes up to max_cfgs values for rave_conv1d_args.config into cfgs and

@@ -312,7 +312,8 @@ STRUCTS = [ConvArgs, AnalysisArgs, SynthesisArgs, FillArgs, RvqArgs, ShiftArgs, 
 # every exported symbol of include/rave_amd.h
 EXPORTS = [
     "rave_last_error", "rave_abi_version", "rave_struct_sizes",
-    "rave_conv1d_chunk", "rave_conv1d_packed_size", "rave_conv1d_pack_weight", "rave_conv1d",
+    "rave_conv1d_chunk", "rave_conv1d_packed_size", "rave_conv1d_pack_weight", "rave_conv1d_pack_weight_device",
+    "rave_conv1d",
     "rave_conv1d_workspace", "rave_conv1d_backward_workspace", "rave_conv1d_backward_data",
     "rave_conv1d_backward_weight", "rave_conv_transpose1d_backward_workspace", "rave_conv_transpose1d_backward_data",
     "rave_conv_transpose1d_backward_weight", "rave_conv1d_configs", "rave_conv1d_split_packed_size", "rave_conv1d_split_pack_weight",
@@ -366,6 +367,7 @@ def _load():
     lib.rave_conv1d_packed_size.argtypes = [C.c_int] * 6
     lib.rave_conv1d_packed_size.restype = i64
     lib.rave_conv1d_pack_weight.argtypes = [vp] + [C.c_int] * 7 + [vp]
+    lib.rave_conv1d_pack_weight_device.argtypes = [vp] + [C.c_int] * 7 + [vp, vp]
     lib.rave_conv1d_workspace.argtypes = [C.POINTER(ConvArgs)]
     lib.rave_conv1d_configs.argtypes = [C.POINTER(ConvArgs), C.POINTER(i32), C.c_int]
     lib.rave_conv1d_split_packed_size.argtypes = [C.c_int] * 6
@@ -585,6 +587,16 @@ def pack_conv_weight(w, c_in, c_out, kernel, stride, dilation, transposed, out_s
     check(pack_fn(w.ctypes.data, c_in, c_out, kernel, stride, dilation,
                   int(transposed), int(out_shift), out.ctypes.data), "pack_weight")
     return out
+
+
+def pack_conv_weight_device(w_ptr, c_in, c_out, kernel, stride, dilation, transposed, out_shift, packed_ptr,
+                            stream=None) -> None:
+    """rave_conv1d_pack_weight_device: the exact-fp32 image of the torch-layout
+    weight at device address ``w_ptr`` into the rave_conv1d_packed_size floats
+    at device address ``packed_ptr`` (no clearing needed), asynchronously on
+    ``stream`` (a hipStream_t as an int; None = the default stream)."""
+    check(lib.rave_conv1d_pack_weight_device(w_ptr, c_in, c_out, kernel, stride, dilation, int(transposed),
+                                             int(out_shift), packed_ptr, stream), "pack_weight_device")
 
 
 def pack_edge_filter(filt, head: bool, n_out_bands: int = 6, f32: bool = False):

@@ -26,10 +26,14 @@ the C-ABI), so a module tree written against ``cc`` runs on the MI355X:
 Weights live in ordinary ``weight`` / ``bias`` parameters (so
 torch.nn.utils.weight_norm and the reference's state_dict names apply); the
 kernels take a packed image made on first use (``prepare()`` re-packs after a
-weight change; in eager Python a changed weight tensor is detected).
+weight change; in eager Python a changed weight tensor is detected).  In exact
+fp32 with the weight on the GPU the image is made by a kernel into the module's
+own buffer (``rave_amd::pack_conv1d_device_``): a training step never takes a
+weight through the host.
 Everything here is TorchScript-scriptable: the custom ops are
 ``torch.ops.rave_amd.*``.  No CPU fallback: the ops need the GPU kernels.
 """
+import weakref
 from typing import List, Optional, Tuple
 
 import torch
@@ -125,7 +129,19 @@ class _PackedConv(nn.Module):
         self.weight = nn.Parameter(ref.weight.detach().clone().reshape(shape))    # torch's default init
         self.bias = nn.Parameter(ref.bias.detach().clone()) if bias else None
         self.register_buffer("packed", torch.zeros(0), persistent=False)
+        # floats of the exact-fp32 image (-1: a shape the kernels do not implement; prepare() raises)
+        self.packed_size = int(torch.ops.rave_amd.conv1d_packed_size(self.c_in, self.c_out, self.kernel, self.stride,
+                                                                     self.dilation, self.transposed))
+        # eager only: the weight tensor the image was made from (a weak reference, compared
+        # with `is`: a dead or different tensor never matches, whatever its address) and its
+        # [data_ptr, _version] at that time
+        self.packed_for = None
         self.packed_key: List[int] = [0, 0]
+
+    def __getstate__(self):
+        state = self.__dict__.copy()
+        state["packed_for"] = None         # a weak reference does not pickle; the next forward repacks
+        return state
 
     @torch.jit.export
     def fused(self) -> Tuple[int, float, Optional[torch.Tensor]]:
@@ -134,21 +150,42 @@ class _PackedConv(nn.Module):
 
     @torch.jit.export
     def prepare(self) -> None:
-        """Pack the current weight (after loading or changing it)."""
+        """Pack the current weight (after loading or changing it).  Exact fp32 with
+        the weight on the GPU: one kernel launch into the module's own ``packed``
+        buffer (allocated once per device), no host copy and no synchronisation.
+        split16, or a weight still on the CPU: the host packer."""
         w = self.weight
-        p = torch.ops.rave_amd.pack_conv1d(w, self.c_in, self.c_out, self.kernel, self.stride, self.dilation,
-                                           self.transposed, self.out_shift, self.precision)
-        self.packed = p.to(w.device)
+        if self.precision == 0 and w.is_cuda and self.packed_size > 0:
+            if self.packed.numel() != self.packed_size or self.packed.device != w.device:
+                self.packed = torch.empty(self.packed_size, dtype=torch.float32, device=w.device)
+            torch.ops.rave_amd.pack_conv1d_device_(w.detach().to(torch.float32).contiguous(), self.packed, self.c_in,
+                                                   self.c_out, self.kernel, self.stride, self.dilation,
+                                                   self.transposed, self.out_shift)
+        else:
+            p = torch.ops.rave_amd.pack_conv1d(w, self.c_in, self.c_out, self.kernel, self.stride, self.dilation,
+                                               self.transposed, self.out_shift, self.precision)
+            self.packed = p.to(w.device)
+        if not torch.jit.is_scripting():
+            self.packed_for = weakref.ref(w)
+            self.packed_key = [w.data_ptr(), w._version]
 
     def _packed_weight(self, x: torch.Tensor) -> torch.Tensor:
+        stale = self.packed.numel() == 0 or self.packed.device != x.device
         if not torch.jit.is_scripting():
-            key = [self.weight.data_ptr(), self.weight._version]
-            if key != self.packed_key:           # weight replaced / modified (eager only)
-                self.packed = torch.zeros(0)
-                self.packed_key = key
-        if self.packed.numel() == 0 or self.packed.device != x.device:
+            w = self.weight
+            if self.precision == 0 and w.is_cuda and self.packed_size > 0:
+                # device pack: one launch into the same buffer on every call, so no key can
+                # go stale (a write through weight.data moves neither the address nor
+                # _version; under weight_norm every forward's weight is a new tensor)
+                stale = True
+            else:
+                # host pack: only when the weight was replaced / modified
+                stale = (stale or self.packed_for is None or self.packed_for() is not w
+                         or self.packed_key != [w.data_ptr(), w._version])
+        if stale:
             self.prepare()
-            self.packed = self.packed.to(x.device)
+            if self.packed.device != x.device:
+                self.packed = self.packed.to(x.device)
         return self.packed
 
 

@@ -337,6 +337,39 @@ at::Tensor pack_conv1d_op(at::Tensor w, int64_t c_in, int64_t c_out, int64_t ker
     return out;
 }
 
+// rave_amd::conv1d_packed_size -- rave_conv1d_packed_size: floats of the exact-fp32
+// image of a layer (-1: a shape the kernels do not implement)
+int64_t conv1d_packed_size_op(int64_t c_in, int64_t c_out, int64_t kernel, int64_t stride, int64_t dilation,
+                              bool transposed) {
+    return rave_conv1d_packed_size((int)c_in, (int)c_out, (int)kernel, (int)stride, (int)dilation, transposed);
+}
+
+// rave_amd::pack_conv1d_device_ -- rave_conv1d_pack_weight_device: the exact-fp32
+// image of a GPU weight into an existing GPU buffer of rave_conv1d_packed_size
+// floats (every float written), one launch on torch's current stream; no host
+// copy, no allocation, no synchronisation.  The weight is read detached: the
+// autograd edge to it is conv1d_w's / conv_transpose1d_w's.
+at::Tensor& pack_conv1d_device_op(const at::Tensor& w, at::Tensor& packed, int64_t c_in, int64_t c_out, int64_t kernel,
+                                  int64_t stride, int64_t dilation, bool transposed, int64_t out_shift) {
+    TORCH_CHECK_VALUE(w.is_cuda() && w.scalar_type() == at::kFloat && w.is_contiguous(),
+                      "w must be a contiguous float32 GPU tensor");
+    TORCH_CHECK_VALUE(packed.is_cuda() && packed.scalar_type() == at::kFloat && packed.is_contiguous(),
+                      "packed must be a contiguous float32 GPU tensor");
+    TORCH_CHECK_VALUE(packed.device() == w.device(), "packed must be on w's device");
+    TORCH_CHECK_VALUE(w.numel() == c_in * c_out * kernel, "weight has ", w.numel(), " values, expected ",
+                      c_in * c_out * kernel);
+    const int64_t n = rave_conv1d_packed_size((int)c_in, (int)c_out, (int)kernel, (int)stride, (int)dilation, transposed);
+    TORCH_CHECK_NOT_IMPLEMENTED(n > 0, "conv1d: unsupported layer shape (c_in ", c_in, ", kernel ", kernel, ", stride ",
+                                stride, ", dilation ", dilation, ")");
+    TORCH_CHECK_VALUE(packed.numel() == n, "packed has ", packed.numel(), " values, expected ", n);
+    c10::hip::HIPGuard g((c10::DeviceIndex)w.get_device());
+    check(rave_conv1d_pack_weight_device(w.data_ptr<float>(), (int)c_in, (int)c_out, (int)kernel, (int)stride,
+                                         (int)dilation, transposed, (int)out_shift, packed.data_ptr<float>(),
+                                         cur_stream(w)),
+          "pack_conv1d_device_");
+    return packed;
+}
+
 // rave_amd::conv1d -- rave_conv1d: act(x) conv W (+ bias) (+ residual).
 // transposed: the polyphase ConvTranspose1d (offline: pad_left 0, out_shift
 // stride/2; cached: x starts with one history column, pad_left 1, out_shift 0).
@@ -982,6 +1015,10 @@ TORCH_LIBRARY(rave_amd, lib) {
     lib.def("fir(Tensor x, Tensor h, int stride, int pad_left, int pad_right, Tensor? hist) -> Tensor", &fir_op);
     lib.def("pack_conv1d(Tensor w, int c_in, int c_out, int kernel, int stride, int dilation, bool transposed, "
             "int out_shift, int precision) -> Tensor", &pack_conv1d_op);
+    lib.def("conv1d_packed_size(int c_in, int c_out, int kernel, int stride, int dilation, bool transposed) -> int",
+            &conv1d_packed_size_op);
+    lib.def("pack_conv1d_device_(Tensor w, Tensor(a!) packed, int c_in, int c_out, int kernel, int stride, int dilation, "
+            "bool transposed, int out_shift) -> Tensor(a!)", &pack_conv1d_device_op);
     lib.def("conv1d(Tensor x, Tensor packed, Tensor? bias, Tensor? alpha, Tensor? residual, int c_out, int kernel, "
             "int stride, int dilation, int pad_left, int pad_right, bool transposed, int out_shift, int act, "
             "float slope, int precision) -> Tensor", &conv1d_op);
