@@ -48,6 +48,9 @@ __device__ __forceinline__ void distance_tile(const DistParams& p, int sc, int l
     constexpr int H = N / 2;
     float* re = lds;
     float* im = lds + G::kConc * N;
+    // nz[2c], nz[2c + 1]: x's / y's frame in slot c has a nonzero sample (see
+    // stft_mag_kernel: a frame of zeros has the spectrum 0, not its partner's noise)
+    __shared__ int nz[2 * G::kConc];
     const float* win = p.table[sc];
     const float2* tw = reinterpret_cast<const float2*>(win + N);
     const int frames = p.frames[sc];
@@ -58,6 +61,8 @@ __device__ __forceinline__ void distance_tile(const DistParams& p, int sc, int l
     for (int pass = 0; pass < G::kPasses; ++pass) {
         const int f0 = f_tile + pass * G::kConc;
         if (f0 >= frames) break;                                  // uniform over the workgroup
+        if (threadIdx.x < 2 * G::kConc) nz[threadIdx.x] = 0;
+        __syncthreads();
 #pragma unroll
         for (int u = 0; u < G::kConc * N / kThreads; ++u) {
             const int e = threadIdx.x + u * kThreads;
@@ -71,6 +76,8 @@ __device__ __forceinline__ void distance_tile(const DistParams& p, int sc, int l
             }
             re[e] = a;
             im[e] = b;
+            if (a != 0.f) nz[2 * (e / N)] = 1;                      // every writer stores the same 1
+            if (b != 0.f) nz[2 * (e / N) + 1] = 1;
         }
         __syncthreads();
         fft_lds<N>(re, im, tw);
@@ -81,12 +88,13 @@ __device__ __forceinline__ void distance_tile(const DistParams& p, int sc, int l
             if (f0 + c >= frames) continue;
             const float* zr = re + c * N;
             const float* zi = im + c * N;
+            const bool xz = nz[2 * c] == 0, yz = nz[2 * c + 1] == 0;
             float mx, my;
             if (k == 0) {
                 // DC and Nyquist are their own mirror: X = Re Z, Y = Im Z
                 mx = fabsf(zr[0]);
                 my = fabsf(zi[0]);
-                const float nx = fabsf(zr[H]), ny = fabsf(zi[H]);
+                const float nx = xz ? 0.f : fabsf(zr[H]), ny = yz ? 0.f : fabsf(zi[H]);
                 const float d = nx - ny;
                 sd += d * d;
                 sx += nx * nx;
@@ -98,6 +106,8 @@ __device__ __forceinline__ void distance_tile(const DistParams& p, int sc, int l
                 mx = 0.5f * sqrtf(xre * xre + xim * xim);
                 my = 0.5f * sqrtf(yre * yre + yim * yim);
             }
+            if (xz) mx = 0.f;
+            if (yz) my = 0.f;
             const float d = mx - my;
             sd += d * d;
             sx += mx * mx;
@@ -197,6 +207,10 @@ __global__ __launch_bounds__(kThreads) void stft_mag_kernel(rave_stft_args a, in
     constexpr int H = N / 2;
     __shared__ float re[G::kConc * N];
     __shared__ float im[G::kConc * N];
+    // nz[2c], nz[2c + 1]: frame 2c / 2c + 1 of the pass has a nonzero sample.  A
+    // frame of zeros transforms to zeros; read back out of the shared FFT it would
+    // come out as its partner's rounding noise instead.
+    __shared__ int nz[2 * G::kConc];
     const float* win = a.table;
     const float2* tw = reinterpret_cast<const float2*>(win + N);
     const int row = blockIdx.y;
@@ -205,6 +219,8 @@ __global__ __launch_bounds__(kThreads) void stft_mag_kernel(rave_stft_args a, in
     for (int pass = 0; pass < G::kPasses; ++pass) {
         const int f0 = 2 * (blockIdx.x * G::kTile + pass * G::kConc);
         if (f0 >= frames) break;
+        if (threadIdx.x < 2 * G::kConc) nz[threadIdx.x] = 0;
+        __syncthreads();
 #pragma unroll
         for (int u = 0; u < G::kConc * N / kThreads; ++u) {
             const int e = threadIdx.x + u * kThreads;
@@ -215,6 +231,8 @@ __global__ __launch_bounds__(kThreads) void stft_mag_kernel(rave_stft_args a, in
             if (fa + 1 < frames) vb = w * xr[reflect((fa + 1) * (N / 4) + j - H, a.t_len)];
             re[e] = va;
             im[e] = vb;
+            if (va != 0.f) nz[2 * (e / N)] = 1;                     // every writer stores the same 1
+            if (vb != 0.f) nz[2 * (e / N) + 1] = 1;
         }
         __syncthreads();
         fft_lds<N>(re, im, tw);
@@ -227,12 +245,13 @@ __global__ __launch_bounds__(kThreads) void stft_mag_kernel(rave_stft_args a, in
             const bool second = fa + 1 < frames;
             const float* zr = re + c * N;
             const float* zi = im + c * N;
+            const bool za = nz[2 * c] == 0, zb = nz[2 * c + 1] == 0;
             float ma, mb;
             if (k == 0) {
                 ma = fabsf(zr[0]);
                 mb = fabsf(zi[0]);
-                yr[(int64_t)H * frames + fa] = fabsf(zr[H]);
-                if (second) yr[(int64_t)H * frames + fa + 1] = fabsf(zi[H]);
+                yr[(int64_t)H * frames + fa] = za ? 0.f : fabsf(zr[H]);
+                if (second) yr[(int64_t)H * frames + fa + 1] = zb ? 0.f : fabsf(zi[H]);
             } else {
                 const float ar = zr[k], ai = zi[k], br = zr[N - k], bi = zi[N - k];
                 const float are = ar + br, aim = ai - bi;
@@ -240,8 +259,8 @@ __global__ __launch_bounds__(kThreads) void stft_mag_kernel(rave_stft_args a, in
                 ma = 0.5f * sqrtf(are * are + aim * aim);
                 mb = 0.5f * sqrtf(bre * bre + bim * bim);
             }
-            yr[(int64_t)k * frames + fa] = ma;
-            if (second) yr[(int64_t)k * frames + fa + 1] = mb;
+            yr[(int64_t)k * frames + fa] = za ? 0.f : ma;
+            if (second) yr[(int64_t)k * frames + fa + 1] = zb ? 0.f : mb;
         }
         __syncthreads();
     }

@@ -91,6 +91,10 @@ __global__ __launch_bounds__(kThreads) void loss_frames_kernel(LossParams p, int
     __shared__ float re[G::kConc * N];
     __shared__ float im[G::kConc * N];
     __shared__ float red[3 * kWaves];
+    // nz[2c], nz[2c + 1]: the value's / the target's frame in slot c has a nonzero
+    // sample.  A frame of zeros has the spectrum 0 (|V| = 0: no gradient); read
+    // back out of the shared FFT it would be the other signal's rounding noise.
+    __shared__ int nz[2 * G::kConc];
     const int local = blockIdx.x;
     float sd = 0.f, st = 0.f, sl = 0.f;
     const float2* tw = reinterpret_cast<const float2*>(p.table[r]);
@@ -111,6 +115,8 @@ __global__ __launch_bounds__(kThreads) void loss_frames_kernel(LossParams p, int
     for (int pass = 0; pass < G::kPasses; ++pass) {
         const int f0 = f_tile + pass * G::kConc;
         if (f0 >= frames) break;                                  // uniform over the workgroup
+        if (threadIdx.x < 2 * G::kConc) nz[threadIdx.x] = 0;
+        __syncthreads();
 #pragma unroll 4
         for (int u = 0; u < G::kConc * N / kThreads; ++u) {
             const int e = threadIdx.x + u * kThreads;
@@ -125,6 +131,8 @@ __global__ __launch_bounds__(kThreads) void loss_frames_kernel(LossParams p, int
             }
             re[e] = a;
             im[e] = b;
+            if (a != 0.f) nz[2 * (e / N)] = 1;                      // every writer stores the same 1
+            if (b != 0.f) nz[2 * (e / N) + 1] = 1;
         }
         __syncthreads();
         fft_lds<N>(re, im, tw);
@@ -137,9 +145,11 @@ __global__ __launch_bounds__(kThreads) void loss_frames_kernel(LossParams p, int
             if (f0 + c >= frames) continue;
             float* zr = re + c * N;
             float* zi = im + c * N;
+            const bool vz = nz[2 * c] == 0, tz = nz[2 * c + 1] == 0;
             if (k == 0) {
                 // DC and Nyquist are their own mirror: V = Re Z, T = Im Z
-                const float v0 = zr[0], t0 = zi[0], vh = zr[H], th = zi[H];
+                const float v0 = vz ? 0.f : zr[0], t0 = tz ? 0.f : zi[0];
+                const float vh = vz ? 0.f : zr[H], th = tz ? 0.f : zi[H];
                 const float g0 = bin_term<BWD>(multires, p.eps, v0 * v0, t0 * t0, c_lin, c_log, sd, st, sl);
                 const float gh = bin_term<BWD>(multires, p.eps, vh * vh, th * th, c_lin, c_log, sd, st, sl);
                 if (BWD) {
@@ -150,8 +160,8 @@ __global__ __launch_bounds__(kThreads) void loss_frames_kernel(LossParams p, int
                 }
             } else {
                 const float ar = zr[k], ai = zi[k], br = zr[N - k], bi = zi[N - k];
-                const float vre = 0.5f * (ar + br), vim = 0.5f * (ai - bi);       // V[k]
-                const float tre = 0.5f * (ai + bi), tim = 0.5f * (br - ar);       // T[k]
+                const float vre = vz ? 0.f : 0.5f * (ar + br), vim = vz ? 0.f : 0.5f * (ai - bi);   // V[k]
+                const float tre = tz ? 0.f : 0.5f * (ai + bi), tim = tz ? 0.f : 0.5f * (br - ar);   // T[k]
                 const float g = bin_term<BWD>(multires, p.eps, vre * vre + vim * vim, tre * tre + tim * tim, c_lin,
                                               c_log, sd, st, sl);
                 if (BWD) {
