@@ -1181,7 +1181,7 @@ int rave_model_op_times(rave_model* m, int which, int batch, int t, float* ms, i
  * hop) with persistent per-layer caches (zeroed at creation and by reset),
  * each conv in its cached form (CachedConv1d / CachedConvTranspose1d,
  * Residual's AlignBranches delays).  Decoded audio lags one-shot decoding by
- * rave_stream_delay samples (928 for v2 causal, 13280 for v2 centred); a
+ * rave_stream_delay samples (928 for v2 causal, 8672 for v2 centred); a
  * causal encoder is exact.  AdaIN statistics are per block, as the reference
  * computes them per call.
  * RAVE_STREAM_GRAPH: each block replays a captured hipGraph (inputs and

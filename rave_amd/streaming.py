@@ -14,7 +14,7 @@ exports with ``--streaming`` (README.md:187-190): every CachedConv1d reads an
 (l + r)-column cache, so it lags its offline conv by r, and Residual's
 AlignBranches delays the identity branch by the unit's delay
 (rave/blocks.py:32-46).  The decoder output equals one-shot decoding delayed
-by ``decode_delay`` samples (928 for v2 causal, 13280 for v2 centred) once the
+by ``decode_delay`` samples (928 for v2 causal, 8672 for v2 centred) once the
 receptive field is filled; a causal encoder is exact (zero delay), a centred
 one decimates its delayed signal on the strided convs' own phase, as the
 reference's does.  Discrete configs stream RVQ indices (``encode_codes`` /
