@@ -72,26 +72,44 @@ inline void launch(K kernel, dim3 grid, dim3 block, uint32_t lds, hipStream_t st
 // launch out of its own L2 instead of another XCD's (via the Infinity Cache).
 // A bijection for any grid, so correctness never depends on the placement.
 __device__ __forceinline__ int xcd_major(int lin, int grid) {
-#ifndef RAVE_LEGACY_MAP
     if ((grid & 7) == 0) return (lin & 7) * (grid >> 3) + (lin >> 3);
-#endif
-    (void)grid;
     return lin;
 }
 
-// Cache-policy bits of the layer-output stores (buffer instruction aux field;
-// 16 = sc1, write-through).  Default: plain stores (the line stays in the
-// writing XCD's L2 for the next kernel's reads).
-// bf16x3 conv weight image (RAVE_BF3_W4, round 5): 0 = three bf16 planes per
-// K-step (6 bytes per weight); 1 = the exact-fp32 ring image (4 bytes per
-// weight, rave_conv1d_ring_pack_weight's layout), split into hi / mid / lo in
-// registers after each fragment load (conv_split.hip, edge_split.hip's tail)
-#ifndef RAVE_BF3_W4
-#define RAVE_BF3_W4 0
-#endif
+// Buffer descriptor from wave-uniform inputs (guide T8/T20).  The 64-bit byte
+// count is for extents a caller sums in 64 bits: clamped to the descriptor's range.
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p, int bytes) {
+    const uint64_t v = reinterpret_cast<uint64_t>(p);
+    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v);
+    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
+    const uint64_t u = ((uint64_t)hi << 32) | lo;
+    return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(u), (short)0,
+                                             __builtin_amdgcn_readfirstlane(bytes), 0x00020000);
+}
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p, int64_t bytes) {
+    return make_rsrc(p, (int)(bytes < 0x7FFFFFF0 ? bytes : 0x7FFFFFF0));
+}
 
-#ifndef RAVE_YAUX
-#define RAVE_YAUX 0
+// An integer as a type: compile-time dispatch through generic lambdas.
+template <int V> struct IC {
+    static constexpr int value = V;
+};
+
+// Diagnostic build only (-DRAVE_STAMPS): thread 0 writes clock stamp k of its
+// workgroup's 8 into the device global g (null: off); slot 7 takes the wall
+// clock beside stamp 0.
+#ifdef RAVE_STAMPS
+#define RAVE_STAMP(g, k)                                                             \
+    do {                                                                             \
+        if (threadIdx.x == 0 && (g)) {                                               \
+            (g)[blockIdx.x * 8 + (k)] = __builtin_amdgcn_s_memtime();                \
+            if ((k) == 0) (g)[blockIdx.x * 8 + 7] = __builtin_amdgcn_s_memrealtime(); \
+        }                                                                            \
+    } while (0)
+#else
+#define RAVE_STAMP(g, k) \
+    do {                 \
+    } while (0)
 #endif
 
 constexpr int ceil_div(int a, int b) { return (a + b - 1) / b; }
@@ -115,8 +133,6 @@ __device__ __forceinline__ float sin_squared(float x) {
     return v * v;
 }
 
-// Split-f16 range guard (RAVE_PREC_SPLIT16).  An operand v is carried as
-// hi = f16(v), lo = f16((v - hi) * 2^11), which needs |v| < 2^15.  Kernels
 // bf16x3 operand split (every kernel's RAVE_PREC_BF16X3 path): v == hi + mid + lo
 // exactly, each a bf16 (RNE: the remainders v - hi and v - hi - mid are exact in
 // fp32).  Worked in pairs: one v_cvt_pk_bf16_f32 per part and pair, the parts
@@ -149,14 +165,13 @@ __device__ __forceinline__ void bf3_split_pk(const FV& v, BV& hi, BV& mid, BV& l
     lo = __builtin_bit_cast(BV, l);
 }
 
+// Split-f16 range guard (RAVE_PREC_SPLIT16).  An operand v is carried as
+// hi = f16(v), lo = f16((v - hi) * 2^11), which needs |v| < 2^15.  Kernels
 // convert optimistically and vote per wave on max |v| >= kSplitLimit; a staged
 // operand block that fails is re-converted as v * 2^-s (s = split_shift of its
 // workgroup-wide max, so |v 2^-s| < 2^14) and the GEMM's accumulator (or the
 // epilogue scale) takes the exact 2^s back.  NaN / inf pass through unscaled,
 // as they do in fp32.
-#ifndef RAVE_SPLIT_GUARD
-#define RAVE_SPLIT_GUARD 1          // 0: A/B variant builds only (no range guard)
-#endif
 constexpr float kSplitLimit = 32768.f;
 __device__ __forceinline__ int split_shift(float m) {
     if (!(m < 3.0e38f)) return 0;
@@ -172,7 +187,6 @@ __device__ __forceinline__ float wave_max(float v) {
 // per-wave votes: wave w's lane 0 writes byte v[w] (0/1) unconditionally after
 // its conversion; after a barrier any wave reads the NW bytes (masked dwords)
 __device__ __forceinline__ void vote_cast(unsigned char* v, int wave, float m) {
-    if (!RAVE_SPLIT_GUARD) return;
     const bool over = __builtin_amdgcn_ballot_w64(m >= kSplitLimit) != 0;
     if ((threadIdx.x & 63) == 0) v[wave] = over ? 1 : 0;
 }
@@ -183,7 +197,6 @@ __device__ __forceinline__ void vote_cast_any(unsigned char* v, int wave, bool b
 }
 template <int NW>
 __device__ __forceinline__ bool vote_any(const unsigned char* v) {
-    if (!RAVE_SPLIT_GUARD) return false;
     const uint32_t* p = reinterpret_cast<const uint32_t*>(v);
     uint32_t x = 0;
 #pragma unroll
@@ -213,6 +226,18 @@ __device__ __forceinline__ float absmax8(const V8& v) {
 #pragma unroll
     for (int i = 1; i < 8; ++i) m = fmaxf(m, fabsf(v[i]));
     return m;
+}
+
+// The fused units' activation with the kind fixed at compile time: Snake, or
+// leaky ReLU as one max (slope <= 1, a host check; slope 1 == none).
+template <bool SNAKE>
+__device__ __forceinline__ float act(float v, float slope, float alpha) {
+    if constexpr (SNAKE) {
+        const float r = 1.0f / (alpha + 1e-9f);
+        return v + r * sin_squared(alpha * v);
+    } else {
+        return fmaxf(v, v * slope);
+    }
 }
 
 // Input-activation prologue shared by the conv and noise kernels.

@@ -32,13 +32,8 @@ typedef float g_f32x2 __attribute__((ext_vector_type(2)));
 typedef float g_f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kGemvStage = 12288;                  // staged window floats per workgroup (48 KiB)
-// in-launch split-K combine by sc1 stores / loads instead of an agent release /
-// acquire pair (round 6; 0 = the fence form, for A/B builds)
-#ifndef RAVE_GEMV_SC1
-#define RAVE_GEMV_SC1 1
-#endif
-constexpr bool kGemvSc1 = RAVE_GEMV_SC1 != 0;
-// dynamic LDS of an sc1 in-launch grid: more than half the CU's 160 KB, so no
+// The in-launch split-K combine hands the slabs over by sc1 stores / loads, not an
+// agent release / acquire pair (round 6).  Dynamic LDS of such a grid: more than half the CU's 160 KB, so no
 // second workgroup of the launch shares the CU (the measured form's condition)
 constexpr size_t kGemvOnePerCu = 80 * 1024 + 256;
 
@@ -207,7 +202,7 @@ __global__ __launch_bounds__(256) void conv1d_gemv_kernel(ConvKArgs a) {
 #pragma unroll
             for (int n = 0; n < NC; ++n) {
                 if (n0 + n >= U) continue;
-                if (kGemvSc1 && a.inlaunch) {
+                if (a.inlaunch) {
                     const int64_t off = (int64_t)split * total + ((int64_t)b * a.M + m) * U + n0 + n;
                     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v[n]), srs, (unsigned)(off * 4), 0,
                                                           16);
@@ -218,7 +213,7 @@ __global__ __launch_bounds__(256) void conv1d_gemv_kernel(ConvKArgs a) {
         if (!a.inlaunch) return;                      // a separate reduce launch sums the slabs
         // in-launch combine: draw the row tile's ticket; the split drawing S - 1
         // sums every slab in split order (bitwise the separate reduce).  Form
-        // (kGemvSc1, the launch keeps one workgroup per CU): MI355X_MICROARCH.md's
+        // (sc1, the launch keeps one workgroup per CU): MI355X_MICROARCH.md's
         // hand-off table row 1 -- every slab byte stored sc1, every storing wave
         // drained before the barrier behind which ONE lane adds to the tile's
         // unsharded counter, the last adder told by the value its add returned,
@@ -228,12 +223,10 @@ __global__ __launch_bounds__(256) void conv1d_gemv_kernel(ConvKArgs a) {
         __syncthreads();
         __shared__ int last_s;
         if (tid == 0) {
-            if constexpr (!kGemvSc1) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
             const int prev = __hip_atomic_fetch_add(a.tickets + tile, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             const int last = prev == a.S - 1;
             if (last) {
                 __hip_atomic_store(a.tickets + tile, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                if constexpr (!kGemvSc1) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
             }
             last_s = last;
         }
@@ -253,7 +246,7 @@ __global__ __launch_bounds__(256) void conv1d_gemv_kernel(ConvKArgs a) {
                 for (int n = 0; n < NC; ++n) {
                     const int64_t off = (int64_t)(s0 + i) * total + ((int64_t)b * a.M + m) * U + n0 + n;
                     t[i][n] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
-                        prs, (s0 + i < a.S && n0 + n < U) ? (unsigned)(off * 4) : kOOB, 0, kGemvSc1 ? 16 : 0));
+                        prs, (s0 + i < a.S && n0 + n < U) ? (unsigned)(off * 4) : kOOB, 0, 16));
                 }
 #pragma unroll
             for (int i = 0; i < SB; ++i)
@@ -284,9 +277,6 @@ __global__ __launch_bounds__(256) void conv1d_gemv_kernel(ConvKArgs a) {
 //     summed by a fixed xor-shuffle tree, the 4 waves through LDS in wave
 //     order: deterministic, no atomics, no slabs.
 constexpr int kRowsStage = 24576;                  // staged window floats (96 KiB)
-#ifndef RAVE_ROWS_XCD
-#define RAVE_ROWS_XCD 1                            // 0: plain block order (A/B builds)
-#endif
 // the wave-sum area after the window (+ slack: lanes read NMAX columns per row)
 __host__ __device__ inline int rows_red_off(int window, int slack) { return ((window + 3) & ~3) + slack + 16; }
 
@@ -302,8 +292,7 @@ __global__ __launch_bounds__(256) void conv1d_gemv_rows_kernel(ConvKArgs a) {
     const int MT = ceil_div(a.M, RT);
     // neighbouring row tiles (which read the same 128-byte weight lines at RT < 32)
     // on one XCD: blocks are dealt round-robin over the 8 XCDs (common.h xcd_major)
-    const int tile = __builtin_amdgcn_readfirstlane(RAVE_ROWS_XCD ? xcd_major((int)blockIdx.x, (int)gridDim.x)
-                                                                   : (int)blockIdx.x);
+    const int tile = __builtin_amdgcn_readfirstlane(xcd_major((int)blockIdx.x, (int)gridDim.x));
     const int mt = tile % MT, b = tile / MT;
     const int m0 = mt * RT;
     const int nch = a.nchunks * CIT;                 // staged channels (all of K)
@@ -495,7 +484,7 @@ static int gemv_go(ConvKArgs k, hipStream_t st) {
     // (+ slack: lanes read all NMAX columns of a window row, the ones past U unused)
     size_t lds = (size_t)std::max(ceil_div(k.cps * GFam<KT>::CIT * k.XW, 4) * 4 + NMAX * GFam<KT>::ST + 16,
                                   4 * GR<NMAX>::BM * NMAX) * 4;
-    if (kGemvSc1 && k.inlaunch) lds = std::max(lds, kGemvOnePerCu);
+    if (k.inlaunch) lds = std::max(lds, kGemvOnePerCu);
     if (lds > 150 * 1024) {
         set_error("conv1d(gemv): staging exceeds the LDS budget");
         return RAVE_ERR_UNSUPPORTED;

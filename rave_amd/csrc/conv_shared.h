@@ -1,5 +1,5 @@
 // Pieces shared by the exact-fp32 (conv1d.hip) and split-f16 (conv_split.hip)
-// implicit-GEMM conv kernels: the kernel argument block, buffer descriptors,
+// implicit-GEMM conv kernels: the kernel argument block,
 // the ConvTranspose row mapping, the epilogue store and the split-K reduce.
 #pragma once
 #include "common.h"
@@ -43,16 +43,6 @@ struct ConvKArgs {
     int gx, gy;                   // split path: column / row tiles per batch item (1-D grid)
     int inlaunch;                 // split path: the last-arriving K-split sums the slabs
 };
-
-// Buffer descriptor from wave-uniform inputs (guide T8/T20).
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const float* p, int bytes) {
-    const uint64_t v = reinterpret_cast<uint64_t>(p);
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v);
-    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
-    const uint64_t u = ((uint64_t)hi << 32) | lo;
-    return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(u), (short)0,
-                                             __builtin_amdgcn_readfirstlane(bytes), 0x00020000);
-}
 
 // --------------------------------------------------------------------- epilogue
 // ConvT row m -> (output channel, phase).  Rows [0, split_row) hold phases

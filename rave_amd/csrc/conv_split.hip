@@ -33,6 +33,7 @@
 // tile's K-steps.  Split-K over workgroups for short-N layers (fp32 slabs,
 // fixed-order combine: deterministic).  The autotuner picks the tile.
 #include "conv_shared.h"
+#include "pack_shared.h"
 
 #include <cmath>
 #include <cstring>
@@ -44,10 +45,6 @@ typedef _Float16 s_h8 __attribute__((ext_vector_type(8)));
 typedef float s_f32x8 __attribute__((ext_vector_type(8)));
 typedef float s_f32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 s_b8 __attribute__((ext_vector_type(8)));
-// fp32 x 8 -> three bf16 parts with v == hi + mid + lo exactly (each remainder exact in fp32)
-__device__ __forceinline__ void s_bf3_split(const s_f32x8& v, s_b8& hi, s_b8& mid, s_b8& lo) {
-    bf3_split_pk(v, hi, mid, lo);
-}
 
 // (taps after polyphase Q, phases S, virtual channels per chunk VC, max row shift)
 template <int KT> struct SFam;
@@ -156,11 +153,10 @@ __device__ __forceinline__ u32x4_t raw_rsrc(const void* p, int bytes) {
 // round, and enough of them for four K-groups on the short-N layers (C >= 512
 // at 64-128 frames), which would otherwise need split-K slabs in HBM.
 // NP: operand planes per staged buffer (2: the split16 (hi, lo) pair or one
-// fp32 plane in its bytes; 3: bf16x3 hi, lo, mid); NPW: 16-byte weight
-// fragment loads per K-step and 32-row block (NP, or 2 for the bf16x3 kernel on
-// the fp32 weight image, RAVE_BF3_W4)
+// fp32 plane in its bytes; 3: bf16x3 hi, lo, mid), and as many 16-byte weight
+// fragment loads per K-step and 32-row block
 template <int KT, int BM, int BN, int WM, bool XV = true, int KG = 1, int WN_ = 4096 / WM, int VCX = 1, int NS_ = 3,
-          int NP = 2, int NPW = (NP == 3 && RAVE_BF3_W4) ? 2 : NP>
+          int NP = 2>
 struct SGeo {
     using F = SFam<KT>;
     static constexpr int Q = F::Q, S = F::S, VC0 = F::VC, VC = VC0 * VCX;
@@ -176,7 +172,7 @@ struct SGeo {
     static constexpr int XW_MAX = BN + (Q - 1) * F::DMAX + (KT == 2 ? 1 : 0);
     static constexpr int PH = VC + 8;                        // halves per plane row (conflict-free b128)
     static constexpr int XPLANE = XW_MAX * PH * 2;           // bytes per f16 plane
-    static constexpr int WR = KS0 * NJ * NPW;                // weight fragment loads per wave per chunk (max)
+    static constexpr int WR = KS0 * NJ * NP;                 // weight fragment loads per wave per chunk (max)
     // raw window rows: XV = 16-byte pieces from a 4-sample-aligned start (row
     // stride rounded up to 4 samples), else 4-byte pieces
     static constexpr int RS_MAX = XV ? ((XW_MAX * S + 3 + 3) / 4) * 4 : XW_MAX * S;
@@ -194,8 +190,8 @@ struct SGeo {
     // of K-steps to land (NS = 2 trades that for room for wider chunks)
     static constexpr int NS = NS_;
     // hand-counted vmcnt waits (kernel body): prologue, end of chunk, weights
-    static constexpr int WAIT_PRO = (NS - 1) * XI + NPW * KS0 * NJ;
-    static constexpr int WAIT_END = (NS - 1) * NPW * KS0 * NJ + (NS - 2) * XI;
+    static constexpr int WAIT_PRO = (NS - 1) * XI + NP * KS0 * NJ;
+    static constexpr int WAIT_END = (NS - 1) * NP * KS0 * NJ + (NS - 2) * XI;
     static constexpr int WAIT_MAX = WAIT_PRO > WAIT_END ? WAIT_PRO : WAIT_END;
     static constexpr int ALPHA = 4096;                       // Snake alphas (<= 1024 channels)
     static constexpr int EROW = WN + 4;                      // epilogue transpose row stride (floats)
@@ -214,13 +210,8 @@ struct SGeo {
     static_assert(KG == 1 || KG == 2 || KG == 4, "K-groups");
     // a configuration is built only if its hand-counted waits fit the vmcnt
     // field, its LDS fits the CU and every K-group has a K-step
-    static constexpr int NPW_ = NPW;
     static constexpr bool VALID = WAIT_MAX <= 63 && WR + XI <= 63 && LDS_ALL <= 160 * 1024 && ks_of(KG - 1) >= 1 &&
                                   (NS == 2 || NS == 3);
-};
-
-template <int V> struct IC {
-    static constexpr int value = V;
 };
 
 // AR: 0 split16; 1 F32: the same machinery with exact fp32 operands
@@ -237,8 +228,6 @@ __device__ __forceinline__ void conv1d_split_body(const ConvKArgs& a) {
     constexpr bool F32 = AR == 1, BF = AR == 2;
     constexpr int NP = BF ? 3 : 2;
     using G = SGeo<KT, BM, BN, WM, XV, KG, WN_, VCX, NS, NP>;
-    constexpr int NPW = G::NPW_;                     // weight fragment loads per K-step and row block
-    constexpr bool W4 = BF && NPW == 2;              // bf16x3 on the fp32 weight image
     constexpr int S = G::S, CPC = G::CPC, PH = G::PH;
     constexpr int NT = G::NT, NW = G::NW, NWT = G::NWT, WGM = G::WGM, G8 = G::G8, XT = G::XT;
     constexpr int NI = G::NI, NJ = G::NJ, WN = G::WN;
@@ -306,8 +295,8 @@ __device__ __forceinline__ void conv1d_split_body(const ConvKArgs& a) {
     const float slope = a.act == RAVE_ACT_LEAKY ? a.slope : 1.0f;
     const u32x4_t wrs = raw_rsrc(a.w, a.w_bytes);
     // packed weights: [packed chunk][32-row block][KSC0 K-steps][hi|lo][64 lanes][8 halves]
-    const unsigned wcstride = (unsigned)(a.MB * KSC0 * NPW) * 1024u;
-    const unsigned wbase = (unsigned)((mw / 32) * KSC0 * NPW) * 1024u + (unsigned)lane * 16u;
+    const unsigned wcstride = (unsigned)(a.MB * KSC0 * NP) * 1024u;
+    const unsigned wbase = (unsigned)((mw / 32) * KSC0 * NP) * 1024u + (unsigned)lane * 16u;
     const uint32_t lds0 = lds_addr(smem);
     char* planes = smem + G::NS * G::STAGE;
     float* alpha_s = reinterpret_cast<float*>(smem + G::NS * G::STAGE + 2 * NP * G::XPLANE);
@@ -366,16 +355,16 @@ __device__ __forceinline__ void conv1d_split_body(const ConvKArgs& a) {
     // this wave's weight fragments: register ring, one chunk ahead (chunks past
     // the packed image read zeros)
     // (slot = this group's local K-step; st = the chunk's K-step)
-    u32x4_t wr[G::KS0][NJ][NPW];
+    u32x4_t wr[G::KS0][NJ][NP];
     // (staged chunk c, K-step st = sub-chunk u, packed K-step s0)
     auto load_w = [&](int c, int slot, int st) __attribute__((always_inline)) {
         const int u = st / KSC0, s0 = st - u * KSC0;
 #pragma unroll
         for (int j = 0; j < NJ; ++j)
 #pragma unroll
-            for (int pl = 0; pl < NPW; ++pl)
+            for (int pl = 0; pl < NP; ++pl)
                 wr[slot][j][pl] = bload16(wrs, wbase + (unsigned)(c * VCX + u) * wcstride +
-                                                   (unsigned)(((j * KSC0 + s0) * NPW + pl) * 1024));
+                                                   (unsigned)(((j * KSC0 + s0) * NP + pl) * 1024));
     };
     // raw window of a stage -> activation (* xs) -> (hi, lo) f16 planes; returns
     // max |act| of the task's values (the range guard's vote input)
@@ -391,18 +380,6 @@ __device__ __forceinline__ void conv1d_split_body(const ConvKArgs& a) {
             const int g = (int)(((unsigned)e * a.xw_magic) >> 24);
             const int w = e - g * XW;
             if (e < ntask) {
-#ifdef RAVE_EXP_NOCVT
-                // timing-only A/B variant (wrong results, never shipped): the planes
-                // arrive ready-made, as a producer-side split would deliver them --
-                // one 16-byte copy per plane row piece instead of act + split
-                if constexpr (AR == 0 || AR == 2) {
-                    const s_h8 r8 = *reinterpret_cast<const s_h8*>(raw + (g * 8 / S) * RS + off0 + w * S);
-                    *reinterpret_cast<s_h8*>(xh + w * PH + g * 8) = r8;
-                    *reinterpret_cast<s_h8*>(xl + w * PH + g * 8) = r8;
-                    if constexpr (AR == 2) *reinterpret_cast<s_h8*>(xm + w * PH + g * 8) = r8;
-                    return m;
-                }
-#endif
                 s_f32x8 v8;
 #pragma unroll
                 for (int v = 0; v < 8; ++v) {
@@ -422,7 +399,7 @@ __device__ __forceinline__ void conv1d_split_body(const ConvKArgs& a) {
                     *reinterpret_cast<s_f32x4*>(xf + w * PH + g * 8 + 4) = s_f32x4{v8[4], v8[5], v8[6], v8[7]};
                 } else if constexpr (BF) {
                     s_b8 hi, mid, lo;
-                    s_bf3_split(v8, hi, mid, lo);
+                    bf3_split_pk(v8, hi, mid, lo);
                     *reinterpret_cast<s_b8*>(xh + w * PH + g * 8) = hi;
                     *reinterpret_cast<s_b8*>(xl + w * PH + g * 8) = lo;
                     *reinterpret_cast<s_b8*>(xm + w * PH + g * 8) = mid;
@@ -450,12 +427,10 @@ __device__ __forceinline__ void conv1d_split_body(const ConvKArgs& a) {
     // conversion meet in LDS, the chunk is re-converted as act * 2^-s and the
     // chunk's K-steps run on acc * 2^-s, scaled back by 2^s after them (exact).
     auto cast_vote = [&](int pb, float m) __attribute__((always_inline)) {
-        if (!RAVE_SPLIT_GUARD) return;
         const bool over = __builtin_amdgcn_ballot_w64(m >= kSplitLimit) != 0;
         if (lane == 0) vote[pb * 16 + wave] = over ? 1 : 0;
     };
     auto read_vote = [&](int pb) __attribute__((always_inline)) {
-        if (!RAVE_SPLIT_GUARD) return false;
         const uint32_t* v = reinterpret_cast<const uint32_t*>(vote + pb * 16);
         return __builtin_amdgcn_readfirstlane((v[0] | v[1] | v[2] | v[3]) != 0u ? 1 : 0) != 0;
     };
@@ -523,7 +498,7 @@ __device__ __forceinline__ void conv1d_split_body(const ConvKArgs& a) {
         constexpr bool guarded = decltype(guardtag)::value != 0;
         constexpr int KS = G::ks_of(GG);                // own K-steps per chunk
         constexpr int ST0 = G::st_of(GG);               // first own K-step
-        constexpr int WR = KS * NJ * NPW, XI = G::XI;
+        constexpr int WR = KS * NJ * NP, XI = G::XI;
 #pragma unroll
         for (int i = 0; i < NS; ++i) issue(c_begin + i, i);
 #pragma unroll
@@ -569,8 +544,8 @@ __device__ __forceinline__ void conv1d_split_body(const ConvKArgs& a) {
 #endif
 #pragma unroll
                 for (int j = 0; j < NJ; ++j) {
-                    if constexpr (BF && !W4) wait_vm_regs3<WR - NPW * NJ + XI>(wr[k][j][0], wr[k][j][1], wr[k][j][2]);
-                    else wait_vm_regs<WR - NPW * NJ + XI>(wr[k][j][0], wr[k][j][1]);
+                    if constexpr (BF) wait_vm_regs3<WR - NP * NJ + XI>(wr[k][j][0], wr[k][j][1], wr[k][j][2]);
+                    else wait_vm_regs<WR - NP * NJ + XI>(wr[k][j][0], wr[k][j][1]);
                 }
 #ifdef RAVE_STAMPS
                 acc_ww += now() - tw0;
@@ -578,20 +553,12 @@ __device__ __forceinline__ void conv1d_split_body(const ConvKArgs& a) {
                 __builtin_amdgcn_sched_barrier(0);
                 const AFrag& g = f[k & 1];
                 if constexpr (BF) {
-                    // the weight parts: from the image, or (W4) split from its 8 fp32 values
                     s_b8 wh[NJ], wl[NJ], wmd[NJ];
 #pragma unroll
                     for (int j = 0; j < NJ; ++j) {
-                        if constexpr (W4) {
-                            const s_f32x4 u0 = __builtin_bit_cast(s_f32x4, wr[k][j][0]);
-                            const s_f32x4 u1 = __builtin_bit_cast(s_f32x4, wr[k][j][1]);
-                            s_bf3_split(s_f32x8{u0[0], u0[1], u0[2], u0[3], u1[0], u1[1], u1[2], u1[3]}, wh[j], wmd[j],
-                                        wl[j]);
-                        } else {
-                            wh[j] = __builtin_bit_cast(s_b8, wr[k][j][0]);
-                            wl[j] = __builtin_bit_cast(s_b8, wr[k][j][1]);
-                            wmd[j] = __builtin_bit_cast(s_b8, wr[k][j][NPW - 1]);
-                        }
+                        wh[j] = __builtin_bit_cast(s_b8, wr[k][j][0]);
+                        wl[j] = __builtin_bit_cast(s_b8, wr[k][j][1]);
+                        wmd[j] = __builtin_bit_cast(s_b8, wr[k][j][NP - 1]);
                     }
                     // smallest products first: (x, w) = hi*lo, lo*hi, mid*mid, hi*mid, mid*hi, hi*hi
 #pragma unroll
@@ -678,7 +645,7 @@ __device__ __forceinline__ void conv1d_split_body(const ConvKArgs& a) {
 #pragma unroll
             for (int j = 0; j < NJ; ++j)
 #pragma unroll
-                for (int pl = 0; pl < NPW; ++pl) ring_keep(wr[k][j][pl]);
+                for (int pl = 0; pl < NP; ++pl) ring_keep(wr[k][j][pl]);
     };
     // Range guard, two attempts: the first runs the plain K loop (no guard
     // code); an operand past the f16 range became inf in its hi half, so it
@@ -697,7 +664,7 @@ __device__ __forceinline__ void conv1d_split_body(const ConvKArgs& a) {
         }
     };
     run_k(IC<0>{});
-    if (RAVE_SPLIT_GUARD && AR == 0) {
+    if (AR == 0) {
         bool bad = false;
 #pragma unroll
         for (int i = 0; i < NI; ++i)
@@ -724,10 +691,7 @@ __device__ __forceinline__ void conv1d_split_body(const ConvKArgs& a) {
     stamp_sum(5, acc_ww);
     stamp_sum(6, acc_we);
 #endif
-#ifndef RAVE_CONV_KGPAR
-#define RAVE_CONV_KGPAR 1
-#endif
-    if constexpr (KG >= 2 && RAVE_CONV_KGPAR != 0) {
+    if constexpr (KG >= 2) {
         // Plain output (no ConvT interleave, no split-K slab, aligned rows), round 6:
         // every K-group parks its partial tile in LDS in the row-major layout the
         // stores read, and every wave -- not only group 0 -- finishes 1/KG of its
@@ -783,7 +747,7 @@ __device__ __forceinline__ void conv1d_split_body(const ConvKArgs& a) {
                 v = v * rs_r[it] + bias_r[it];
                 if (m < a.M && n + 3 < a.U) {
                     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, v + rv[it]), yrs,
-                                                           (unsigned)(m * a.y_sc + n) * 4u, 0, RAVE_YAUX);
+                                                           (unsigned)(m * a.y_sc + n) * 4u, 0, 0);
                 } else {
                     float vv[4];
                     *reinterpret_cast<s_f32x4*>(vv) = v;
@@ -793,7 +757,7 @@ __device__ __forceinline__ void conv1d_split_body(const ConvKArgs& a) {
                         const float rsd = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
                             rrs, ok ? (unsigned)(m * a.r_sc + n + e) * 4u : kOOB, 0, 0));
                         __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, vv[e] + rsd), yrs,
-                                                              ok ? (unsigned)(m * a.y_sc + n + e) * 4u : kOOB, 0, RAVE_YAUX);
+                                                              ok ? (unsigned)(m * a.y_sc + n + e) * 4u : kOOB, 0, 0);
                     }
                 }
             }
@@ -957,7 +921,7 @@ __device__ __forceinline__ void conv1d_split_body(const ConvKArgs& a) {
                         if (a.bias) v += a.bias[m];
                         if (a.res) v += rv[it];
                         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, v), yrs,
-                                                               (unsigned)(m * a.y_sc + n) * 4u, 0, RAVE_YAUX);
+                                                               (unsigned)(m * a.y_sc + n) * 4u, 0, 0);
                     }
                 }
             } else {
@@ -993,7 +957,7 @@ __device__ __forceinline__ void conv1d_split_body(const ConvKArgs& a) {
                 const s_f32x4 v = *reinterpret_cast<const s_f32x4*>(et + r * G::EROW + cc) + rv[it];
                 if (m < a.M && n + 3 < a.U) {
                     __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, v), yrs,
-                                                           (unsigned)(m * a.y_sc + n) * 4u, 0, RAVE_YAUX);
+                                                           (unsigned)(m * a.y_sc + n) * 4u, 0, 0);
                 } else {
                     float vv[4];
                     *reinterpret_cast<s_f32x4*>(vv) = *reinterpret_cast<const s_f32x4*>(et + r * G::EROW + cc);
@@ -1003,7 +967,7 @@ __device__ __forceinline__ void conv1d_split_body(const ConvKArgs& a) {
                         const float rs = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
                             rrs, ok ? (unsigned)(m * a.r_sc + n + e) * 4u : kOOB, 0, 0));
                         __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, vv[e] + rs), yrs,
-                                                              ok ? (unsigned)(m * a.y_sc + n + e) * 4u : kOOB, 0, RAVE_YAUX);
+                                                              ok ? (unsigned)(m * a.y_sc + n + e) * 4u : kOOB, 0, 0);
                     }
                 }
             }
@@ -1019,7 +983,7 @@ __device__ __forceinline__ void conv1d_split_body(const ConvKArgs& a) {
                     const float rs = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
                         rrs, ok ? (unsigned)(m * a.r_sc + n + e) * 4u : kOOB, 0, 0));
                     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, vp[e] + rs), yrs,
-                                                          ok ? (unsigned)(m * a.y_sc + n + e) * 4u : kOOB, 0, RAVE_YAUX);
+                                                          ok ? (unsigned)(m * a.y_sc + n + e) * 4u : kOOB, 0, 0);
                 }
             }
         }
@@ -1041,7 +1005,7 @@ __device__ __forceinline__ void conv1d_split_body(const ConvKArgs& a) {
                     const int n = n0 + wn * WN + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
                     const int t = n * a.R + q;
                     const unsigned off = (rowok && n < a.U && t < a.t_y) ? (unsigned)(co * a.y_sc + t) * 4u : kOOB;
-                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, acc[i][j][r] + bv), yrs, off, 0, RAVE_YAUX);
+                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, acc[i][j][r] + bv), yrs, off, 0, 0);
                 }
         }
         stamp(4);
@@ -1223,8 +1187,6 @@ __global__ __launch_bounds__(256) void split_reduce_kernel(ConvKArgs a) {
 // combine) when the output alone cannot give every SIMD a wave.
 // operand planes / weight fragments per K-step of an arithmetic (bf16x3: three)
 static int split_planes(int precision) { return precision == RAVE_PREC_BF16X3 ? 3 : 2; }
-// 16-byte weight fragments per K-step and row block in the packed image
-static int split_wplanes(int precision) { return precision == RAVE_PREC_BF16X3 && !RAVE_BF3_W4 ? 3 : 2; }
 static inline int tile_waves(int ti) {   // waves per workgroup
     const int* t = kSplitTiles[ti];
     return (t[0] / t[2]) * (t[1] / t[4]) * t[3];
@@ -1313,7 +1275,7 @@ static int split_prepare(const rave_conv1d_args& a, ConvKArgs& k, int& taps) {
     k.nchunks = ceil_div(a.c_in, split_cpc(taps));
     k.Mpad = ceil_div(k.M, 128) * 128;
     k.MB = k.Mpad / 32;
-    const int64_t frag_floats = (int64_t)k.nchunks * k.MB * split_ksc(taps) * split_wplanes(a.precision) * 256;
+    const int64_t frag_floats = (int64_t)k.nchunks * k.MB * split_ksc(taps) * split_planes(a.precision) * 256;
     RAVE_CHECK_ARG(frag_floats * 4 < (1ll << 31), "conv1d(split16): packed weight beyond 2 GiB");
     k.w_bytes = (int)(frag_floats * 4);
     k.rscale = a.weight + frag_floats;                 // after the fragments
@@ -1427,20 +1389,11 @@ int conv1d_split(const rave_conv1d_args& a, void* stream) {
     return launch_status("split_reduce_kernel");
 }
 
-// ------------------------------------------------------------ weight packing
-// Power-of-two row exponent: max |w * 2^e| in [8, 16) (e = 0 for an all-zero row).
-static int row_exponent(double amax) {
-    if (!(amax > 0.0)) return 0;
-    int e = (int)std::floor(std::log2(16.0 / amax));
-    while (std::ldexp(amax, e) >= 16.0) --e;
-    while (std::ldexp(amax, e) < 8.0) ++e;
-    return e;
-}
-
 }  // namespace rave
 
 using namespace rave;
 
+// ------------------------------------------------------------ weight packing
 // GEMM-row geometry of a layer (shared by the size query and the packer)
 static int split_geometry(int c_in, int c_out, int kernel, int stride, int dilation, int transposed,
                           int out_shift, int& taps, int& M, int& Mpad, int& nchunks, int& split_row,
@@ -1474,7 +1427,7 @@ static int64_t split_packed_floats(int c_in, int c_out, int kernel, int stride, 
         if (split_geometry(c_in, c_out, kernel, stride, dilation, transposed, os ? stride / 2 : 0, taps, M,
                            Mpad, nchunks, split_row, q0) != 0)
             return -1;
-        const int64_t n = (int64_t)nchunks * (Mpad / 32) * split_ksc(taps) * np * 256 + Mpad;
+        const int64_t n = packed_floats((int64_t)nchunks * (Mpad / 32) * split_ksc(taps), np, Mpad);
         best = std::max(best, n);
     }
     return best;
@@ -1487,28 +1440,13 @@ extern "C" int64_t rave_conv1d_split_packed_size(int c_in, int c_out, int kernel
 
 extern "C" int64_t rave_conv1d_bf3_packed_size(int c_in, int c_out, int kernel, int stride, int dilation,
                                                int transposed) {
-    return split_packed_floats(c_in, c_out, kernel, stride, dilation, transposed, RAVE_BF3_W4 ? 2 : 3);
-}
-
-// host fp32 -> bf16, round to nearest even (finite weights)
-static uint16_t bf16_bits(float f) {
-    uint32_t u;
-    std::memcpy(&u, &f, 4);
-    u += 0x7FFFu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
-}
-static float bf16_value(uint16_t h) {
-    const uint32_t u = (uint32_t)h << 16;
-    float f;
-    std::memcpy(&f, &u, 4);
-    return f;
+    return split_packed_floats(c_in, c_out, kernel, stride, dilation, transposed, 3);
 }
 
 static int split_pack(const float* w, int c_in, int c_out, int kernel, int stride, int dilation, int transposed,
-                      int out_shift, float* packed, int mode) {   // 0 split16, 1 fp32, 2 bf16x3
+                      int out_shift, float* packed, int mode) {   // PackMode
     RAVE_CHECK_ARG(w && packed, "split_pack_weight: null pointer");
     const bool f32 = mode != 0;                        // (row scales 1)
-    const int NPW = mode == 2 ? 3 : 2;
     RAVE_CHECK_ARG(c_in > 0 && c_out > 0 && kernel > 0 && stride > 0 && dilation > 0,
                    "split_pack_weight: bad shape");
     RAVE_CHECK_ARG(!transposed || out_shift == 0 || out_shift == stride / 2,
@@ -1550,62 +1488,39 @@ static int split_pack(const float* w, int c_in, int c_out, int kernel, int strid
             for (int j = 0; j < KT_orig; ++j) amax = std::max(amax, (double)std::fabs(wval(m, ci, j)));
         ex[m] = row_exponent(amax);
     }
-    _Float16* out = reinterpret_cast<_Float16*>(packed);
-    uint16_t* bout = reinterpret_cast<uint16_t*>(packed);
+    // fragment ((chunk c, 32-row block mb), K-step st): lane l holds row l & 31,
+    // element e virtual channel 16 hv + 8 (l >> 5) + e of tap q
     for (int c = 0; c < nchunks; ++c)
         for (int mb = 0; mb < MB; ++mb)
             for (int st = 0; st < KSC; ++st) {
                 const int q = st / HPS, hv = st % HPS;
-                const int64_t blk = ((int64_t)(c * MB + mb) * KSC + st) * NPW;   // 1 KB slots
-                uint16_t* bp = bout + blk * 512;       // bf16x3: hi, lo, mid
-                _Float16* hi = out + blk * 512;
-                _Float16* lo = hi + 512;
-                float* f32s = packed + blk * 256;      // fp32: floats 0-3 of a lane in slot 0, 4-7 in slot 1
+                const int64_t frag = (int64_t)(c * MB + mb) * KSC + st;
                 for (int l = 0; l < 64; ++l)
                     for (int e = 0; e < 8; ++e) {
                         const int m = mb * 32 + (l & 31);
-                        const int vc = hv * 16 + 8 * (l >> 5) + e;
                         int ci, j;
-                        kmap(c, q, vc, ci, j);
-                        if (mode == 2) {
-                            const float v = wval(m, ci, j);
-                            const uint16_t h = bf16_bits(v);
-                            const float r = v - bf16_value(h);
-                            const uint16_t md = bf16_bits(r);
-                            bp[l * 8 + e] = h;
-                            bp[1024 + l * 8 + e] = md;
-                            bp[512 + l * 8 + e] = bf16_bits(r - bf16_value(md));
-                            continue;
-                        }
-                        if (f32) {
-                            f32s[(e >> 2) * 256 + l * 4 + (e & 3)] = wval(m, ci, j);
-                            continue;
-                        }
-                        const float v = std::ldexp(wval(m, ci, j), ex[m]);
-                        const _Float16 vh = (_Float16)v;
-                        const _Float16 vl = (_Float16)((v - (float)vh) * 2048.0f);
-                        hi[l * 8 + e] = vh;
-                        lo[l * 8 + e] = vl;
+                        kmap(c, q, hv * 16 + 8 * (l >> 5) + e, ci, j);
+                        const float v = wval(m, ci, j);
+                        put_fragment(packed, frag, mode, l, e, f32 ? v : std::ldexp(v, ex[m]));
                     }
             }
-    float* rs = packed + (int64_t)nchunks * MB * KSC * NPW * 256;
+    float* rs = packed + packed_floats((int64_t)nchunks * MB * KSC, pack_planes(mode), 0);
     for (int m = 0; m < Mpad; ++m) rs[m] = f32 ? 1.0f : (float)std::ldexp(1.0, -(ex[m] + 11));
     return RAVE_OK;
 }
 
 extern "C" int rave_conv1d_split_pack_weight(const float* w, int c_in, int c_out, int kernel, int stride,
                                              int dilation, int transposed, int out_shift, float* packed) {
-    return split_pack(w, c_in, c_out, kernel, stride, dilation, transposed, out_shift, packed, 0);
+    return split_pack(w, c_in, c_out, kernel, stride, dilation, transposed, out_shift, packed, kPackSplit16);
 }
 
 extern "C" int rave_conv1d_ring_pack_weight(const float* w, int c_in, int c_out, int kernel, int stride,
                                             int dilation, int transposed, int out_shift, float* packed) {
-    return split_pack(w, c_in, c_out, kernel, stride, dilation, transposed, out_shift, packed, 1);
+    return split_pack(w, c_in, c_out, kernel, stride, dilation, transposed, out_shift, packed, kPackF32);
 }
 
-// (RAVE_BF3_W4: the bf16x3 kernels read the exact-fp32 image and split it in registers)
 extern "C" int rave_conv1d_bf3_pack_weight(const float* w, int c_in, int c_out, int kernel, int stride,
                                            int dilation, int transposed, int out_shift, float* packed) {
-    return split_pack(w, c_in, c_out, kernel, stride, dilation, transposed, out_shift, packed, RAVE_BF3_W4 ? 1 : 2);
+    return split_pack(w, c_in, c_out, kernel, stride, dilation, transposed, out_shift, packed, kPackBf16x3);
 }
 #endif  // RAVE_SPLIT_KT

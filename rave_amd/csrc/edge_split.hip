@@ -37,6 +37,7 @@
 // with |v 2^-s| < 2^15), so no f16 half overflows; the epilogues undo the
 // scales exactly.  The tail's synthesis input is tanh-bounded.
 #include "common.h"
+#include "pack_shared.h"
 
 #include <algorithm>
 #include <cmath>
@@ -81,16 +82,6 @@ struct EdgeGeo {
     int64_t w_frag_floats;     // floats of fragments before the row scales
 };
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t e_rsrc(const void* p, int64_t bytes) {
-    const uint64_t v = reinterpret_cast<uint64_t>(p);
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v);
-    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
-    const uint64_t u = ((uint64_t)hi << 32) | lo;
-    const int nb = (int)std::min<int64_t>(bytes, 0x7FFFFFF0);
-    return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(u), (short)0,
-                                             __builtin_amdgcn_readfirstlane(nb), 0x00020000);
-}
-
 __device__ __forceinline__ void e_split(float v, _Float16& hi, _Float16& lo) {
     hi = (_Float16)v;
     lo = (_Float16)((v - (float)hi) * 2048.0f);
@@ -129,10 +120,6 @@ struct EdgeW {
 #else
 #define EDGE_STOP(n, v)
 #endif
-
-template <int V> struct EdgeN {
-    static constexpr int value = V;
-};
 
 // =================================================================== encoder head
 // A workgroup owns kHF conv output frames [n0, n0 + kHF) of one batch item:
@@ -425,7 +412,7 @@ __global__ __launch_bounds__(kEdgeNT) void encoder_head_kernel(rave_edge_args a,
         *reinterpret_cast<e_h4*>(bl + row * kHBP + 4 * (g & 1)) = lv4;
     };
     // the conv's weight fragments (no data dependence): in flight across the band barrier
-    const EdgeW W{e_rsrc(a.weight, (int64_t)geo.w_bytes), geo.w_mb};
+    const EdgeW W{make_rsrc(a.weight, (int64_t)geo.w_bytes), geo.w_mb};
     const int MB = (a.conv_c_out + 31) / 32;        // 1 or 2 row blocks
     e_h8 wr[kEdgeK7][2][2];
 #pragma unroll
@@ -535,33 +522,22 @@ constexpr int kTPlane = 2 * kTXR * kTXP;            // halves of the two act(x) 
 static_assert(2 * kTSW * kTSP <= kTPlane, "synthesis planes reuse the act(x) planes");
 constexpr int kTailLds = (2 * 16 * kEdgeFP + kTPlane) * 2 + 2 * kEdgeWaves * 4 + 16;
 // bf16x3 (AR = 2): three act(x) planes from byte 0, no filter in LDS during
-// the conv; after it (planes dead) the fp32 synthesis planes at 0, the K-split
-// partial tiles after them, and the fp32 filter at kTailBfFilt
-constexpr int kTailBfX = 3 * kTXR * kTXP * 2;                  // bytes of the three act(x) planes
-constexpr int kTailBfFilt = 61440;
-constexpr int kTailLdsBf = kTailBfX + 2 * kEdgeWaves * 4 + 16;
-static_assert(kTailBfFilt >= 2 * kTSW * kTSP * 2 + kEdgeWaves * 16 * 64 * 4 &&
-              kTailBfFilt + 16 * kEdgeFP * 4 <= kTailBfX, "bf16x3 tail LDS reuse");
-// bf16x3 synthesis (RAVE_TAIL_BF3_SYN, round 6): the synthesis on the bf16
-// matrix cores too -- three bf16 planes of the synthesis input at 0, the K-split
+// the conv; after it (planes dead) the synthesis runs on the bf16 matrix cores
+// too (round 6): three bf16 planes of the synthesis input at 0, the K-split
 // partial tiles after them, the filter's three bf16 planes at kTailBsFilt (split
 // in-kernel from the exact fp32 image); six v_mfma_f32_16x16x32_bf16 per 32-deep
-// K-step instead of eight v_mfma_f32_16x16x4_f32 per 4-deep one
-#ifndef RAVE_TAIL_BF3_SYN
-#define RAVE_TAIL_BF3_SYN 1
-#endif
+// K-step
+constexpr int kTailBfX = 3 * kTXR * kTXP * 2;                  // bytes of the three act(x) planes
+constexpr int kTailLdsBf = kTailBfX + 2 * kEdgeWaves * 4 + 16;
 constexpr int kTailBsFilt = 75776;
 static_assert(kTailBsFilt >= 3 * kTSW * kTSP * 2 + kEdgeWaves * 16 * 64 * 4 &&
               kTailBsFilt + 3 * 16 * kEdgeFP * 2 <= kTailBfX, "bf16x3 synthesis LDS reuse");
 
-// AR: 0 split-f16, 1 exact fp32, 2 bf16x3 conv (fp32 on the bf16 matrix cores,
-// exact three-way operand split, six bf16 MFMAs per 16-deep K-step) with the
-// exact-fp32 synthesis
+// AR: 0 split-f16, 1 exact fp32, 2 bf16x3 conv and synthesis (fp32 on the bf16
+// matrix cores, exact three-way operand split, six bf16 MFMAs per K-step)
 template <bool SNAKE, bool AM, int AR>
 __global__ __launch_bounds__(kEdgeNT) void decoder_tail_kernel(rave_edge_args a, EdgeGeo geo) {
     constexpr bool F32 = AR == 1, BF = AR == 2;
-    constexpr bool BS = BF && RAVE_TAIL_BF3_SYN != 0;            // BS: bf16x3 synthesis stage
-    constexpr bool FS = AR != 0 && !BS;                          // FS: exact-fp32 synthesis stage
     const int tiles = geo.tiles;
     extern __shared__ __attribute__((aligned(16))) char e_smem[];
     _Float16* fh = reinterpret_cast<_Float16*>(e_smem);          // [16][kEdgeFP] synthesis filter
@@ -573,10 +549,10 @@ __global__ __launch_bounds__(kEdgeNT) void decoder_tail_kernel(rave_edge_args a,
     _Float16* sl = xh + kTSW * kTSP;
     float* red = reinterpret_cast<float*>(BF ? reinterpret_cast<char*>(e_smem) + kTailBfX
                                              : reinterpret_cast<char*>(xh + kTPlane));
-    float* ff = reinterpret_cast<float*>(BF ? e_smem + kTailBfFilt : e_smem);   // FS: [16][kEdgeFP]
+    float* ff = reinterpret_cast<float*>(e_smem);                 // F32: [16][kEdgeFP] synthesis filter
     float* xf = reinterpret_cast<float*>(xh);                     // F32: [kTXR][kTXP] act(x)
-    float* sf = xf;                                                // FS: [kTSW][kTSP] (after the conv)
-    // BS: synthesis input planes [kTSW][kTSP] (hi, lo, mid) and filter planes [16][kEdgeFP] (hi, mid, lo)
+    float* sf = xf;                                                // F32: [kTSW][kTSP] (after the conv)
+    // BF: synthesis input planes [kTSW][kTSP] (hi, lo, mid) and filter planes [16][kEdgeFP] (hi, mid, lo)
     __bf16* sbh = reinterpret_cast<__bf16*>(xh);
     __bf16* sbl = sbh + kTSW * kTSP;
     __bf16* sbm = sbl + kTSW * kTSP;
@@ -596,8 +572,8 @@ __global__ __launch_bounds__(kEdgeNT) void decoder_tail_kernel(rave_edge_args a,
 
     unsigned char* vote = reinterpret_cast<unsigned char*>(red + 2 * kEdgeWaves);
     // ---- the conv's first weight fragments (no data dependence): issued first
-    constexpr int NPW = BF && !RAVE_BF3_W4 ? 3 : 2;   // weight fragments per tap (W4: fp32 image)
-    const EdgeW W{e_rsrc(a.weight, (int64_t)geo.w_bytes), geo.w_mb, NPW};
+    constexpr int NPW = BF ? 3 : 2;                   // weight fragments per tap
+    const EdgeW W{make_rsrc(a.weight, (int64_t)geo.w_bytes), geo.w_mb, NPW};
     constexpr int KS = (kTC / 16) * kEdgeK7;          // 28 K-steps
     constexpr int RING = 4;
     e_h8 wr[RING][NPW];
@@ -708,18 +684,8 @@ __global__ __launch_bounds__(kEdgeNT) void decoder_tail_kernel(rave_edge_args a,
             const int xo = row * kTXP + 16 * ch + 8 * h;
             const e_b8 xh8 = *reinterpret_cast<const e_b8*>(xh + xo), xl8 = *reinterpret_cast<const e_b8*>(xl + xo),
                        xm8 = *reinterpret_cast<const e_b8*>(xm + xo);
-            e_b8 wh, wl, wm;
-            if constexpr (RAVE_BF3_W4) {     // the fp32 image's 8 values -> hi / mid / lo
-                const e_f32x8 w8 = EdgeW::f32(bh8, bl8);
-                wh = __builtin_convertvector(w8, e_b8);
-                const e_f32x8 r = w8 - __builtin_convertvector(wh, e_f32x8);
-                wm = __builtin_convertvector(r, e_b8);
-                wl = __builtin_convertvector(r - __builtin_convertvector(wm, e_f32x8), e_b8);
-            } else {
-                wh = __builtin_bit_cast(e_b8, bh8);
-                wl = __builtin_bit_cast(e_b8, bl8);
-                wm = __builtin_bit_cast(e_b8, bm8);
-            }
+            const e_b8 wh = __builtin_bit_cast(e_b8, bh8), wl = __builtin_bit_cast(e_b8, bl8),
+                       wm = __builtin_bit_cast(e_b8, bm8);
             c0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xl8, wh, c0, 0, 0, 0);
             c0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xh8, wl, c0, 0, 0, 0);
             c0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xm8, wm, c0, 0, 0, 0);
@@ -760,7 +726,7 @@ __global__ __launch_bounds__(kEdgeNT) void decoder_tail_kernel(rave_edge_args a,
     acc += acl;
     acc_x += acl_x;
     __syncthreads();                                 // act(x) planes dead
-    if constexpr (BS) {                              // the filter as three bf16 planes (read after the epilogue's barrier)
+    if constexpr (BF) {                              // the filter as three bf16 planes (read after the epilogue's barrier)
 #pragma unroll
         for (int i = 0; i < FQ; ++i) {
             const int k = tid + i * kEdgeNT;
@@ -772,17 +738,10 @@ __global__ __launch_bounds__(kEdgeNT) void decoder_tail_kernel(rave_edge_args a,
                 *reinterpret_cast<e_b4*>(fbl + 4 * k) = lo;
             }
         }
-    } else if constexpr (BF) {                       // the fp32 filter into its place (read after the epilogue's barrier)
-        e_h8* dst = reinterpret_cast<e_h8*>(ff);
-#pragma unroll
-        for (int i = 0; i < FQ; ++i) {
-            const int k = tid + i * kEdgeNT;
-            if (k < kEdgeFilterHalves / 8) dst[k] = fq[i];
-        }
     }
     // the K-split blocks' partial tiles -> LDS (past the synthesis planes), summed
     // in chunk order by waves 0 (block 8) and 4 (block 9)
-    float* part = reinterpret_cast<float*>(xh + (BS ? 3 : 2) * kTSW * kTSP);
+    float* part = reinterpret_cast<float*>(xh + (BF ? 3 : 2) * kTSW * kTSP);
 #pragma unroll
     for (int r = 0; r < 16; ++r) part[(wave * 16 + r) * 64 + lane] = acc_x[r];
     __syncthreads();
@@ -831,7 +790,7 @@ __global__ __launch_bounds__(kEdgeNT) void decoder_tail_kernel(rave_edge_args a,
             out = 1.0f - 2.0f * __builtin_amdgcn_rcpf(__expf(2.0f * out) + 1.0f);
             if ((c_out & 1) && !(f & 1)) out = -out;
             if (w < kTSW) {
-                if constexpr (BS) {
+                if constexpr (BF) {
                     const float v = ok ? out : 0.f;
                     const __bf16 hi = (__bf16)v;
                     const float r = v - (float)hi;
@@ -839,7 +798,7 @@ __global__ __launch_bounds__(kEdgeNT) void decoder_tail_kernel(rave_edge_args a,
                     sbh[w * kTSP + c_out] = hi;
                     sbm[w * kTSP + c_out] = mid;
                     sbl[w * kTSP + c_out] = (__bf16)(r - (float)mid);
-                } else if constexpr (FS) {
+                } else if constexpr (F32) {
                     sf[w * kTSP + c_out] = ok ? out : 0.f;
                 } else {
                     e_split(ok ? out : 0.f, sh[w * kTSP + c_out], sl[w * kTSP + c_out]);
@@ -863,7 +822,7 @@ __global__ __launch_bounds__(kEdgeNT) void decoder_tail_kernel(rave_edge_args a,
     for (int s = 0; s < kEdgeKW / 32; ++s) {
         const int ka = col * kEdgeFP + 32 * s + 8 * g;
         const int tap = 2 * s + (g >> 1);
-        if constexpr (BS) {
+        if constexpr (BF) {
             // smallest products first (A = filter part, B = signal part): lo*hi, hi*lo,
             // mid*mid, mid*hi, hi*mid, hi*hi
             const e_b8 fh8 = *reinterpret_cast<const e_b8*>(fbh + ka), fm8 = *reinterpret_cast<const e_b8*>(fbm + ka),
@@ -883,7 +842,7 @@ __global__ __launch_bounds__(kEdgeNT) void decoder_tail_kernel(rave_edge_args a,
             }
             continue;
         }
-        if constexpr (FS) {
+        if constexpr (F32) {
             const e_f32x8 af = e_ld8(ff + ka);
 #pragma unroll
             for (int q = 0; q < BLK; ++q) {
@@ -952,14 +911,6 @@ static int edge_lds_attr(K kern, int lds, bool& done) {
 }
 
 // ------------------------------------------------------------ filter images
-static int edge_row_exponent(double amax) {   // max |h 2^e| in [8, 16)
-    if (!(amax > 0.0)) return 0;
-    int e = (int)std::floor(std::log2(16.0 / amax));
-    while (std::ldexp(amax, e) >= 16.0) --e;
-    while (std::ldexp(amax, e) < 8.0) ++e;
-    return e;
-}
-
 // A[r][k] (16 rows x kEdgeKW, zero beyond) -> hi / lo planes + 2^-(e + 11);
 // f32: one fp32 plane [16][kEdgeFP] in the same bytes, then 1
 template <typename Fn>
@@ -974,15 +925,13 @@ static void edge_filter_image(Fn&& A, float* image, bool f32) {
     double amax = 0.0;
     for (int r = 0; r < 16; ++r)
         for (int k = 0; k < kEdgeKW; ++k) amax = std::max(amax, std::fabs((double)A(r, k)));
-    const int e = edge_row_exponent(amax);
+    const int e = row_exponent(amax);
     _Float16* hi = reinterpret_cast<_Float16*>(image);
     _Float16* lo = hi + 16 * kEdgeFP;
     for (int r = 0; r < 16; ++r)
         for (int k = 0; k < kEdgeFP; ++k) {
             const float v = k < kEdgeKW ? (float)std::ldexp((double)A(r, k), e) : 0.f;
-            const _Float16 vh = (_Float16)v;
-            hi[r * kEdgeFP + k] = vh;
-            lo[r * kEdgeFP + k] = (_Float16)((v - (float)vh) * 2048.0f);
+            split_f16(v, hi[r * kEdgeFP + k], lo[r * kEdgeFP + k]);
         }
     image[kEdgeFilterHalves / 2] = (float)std::ldexp(1.0, -(e + 11));
     for (int i = kEdgeFilterHalves / 2 + 1; i < kEdgeFilterFloats; ++i) image[i] = 0.f;
@@ -1096,7 +1045,7 @@ extern "C" int rave_decoder_tail(const rave_edge_args* p, void* stream) {
     if (rc != RAVE_OK) return rc;
     const bool bf = a.precision == RAVE_PREC_BF16X3;
     const int ar = bf ? 2 : f32 ? 1 : 0;
-    const EdgeGeo g = edge_geometry(a, kTF, bf && !RAVE_BF3_W4 ? 3 : 2);
+    const EdgeGeo g = edge_geometry(a, kTF, bf ? 3 : 2);
     const dim3 grid(g.tiles * a.batch);
     const bool snake = a.act == RAVE_ACT_SNAKE, am = a.mode == 1;
     auto pick = [&](auto art) {
@@ -1104,7 +1053,7 @@ extern "C" int rave_decoder_tail(const rave_edge_args* p, void* stream) {
         return snake ? (am ? decoder_tail_kernel<true, true, AR> : decoder_tail_kernel<true, false, AR>)
                      : (am ? decoder_tail_kernel<false, true, AR> : decoder_tail_kernel<false, false, AR>);
     };
-    auto kern = ar == 2 ? pick(EdgeN<2>{}) : ar == 1 ? pick(EdgeN<1>{}) : pick(EdgeN<0>{});
+    auto kern = ar == 2 ? pick(IC<2>{}) : ar == 1 ? pick(IC<1>{}) : pick(IC<0>{});
     const int lds = bf ? kTailLdsBf : kTailLds;
     static bool attr[12] = {false, false, false, false, false, false, false, false, false, false, false, false};
     rc = edge_lds_attr(kern, lds, attr[4 * ar + 2 * snake + am]);

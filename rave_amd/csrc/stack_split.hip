@@ -40,12 +40,6 @@ typedef float ss_f32x16 __attribute__((ext_vector_type(16)));
 typedef __bf16 ss_b8 __attribute__((ext_vector_type(8)));
 typedef __bf16 ss_b4 __attribute__((ext_vector_type(4)));
 
-// fp32 -> three bf16 parts with v == hi + mid + lo exactly (unit_split.hip)
-template <typename FV, typename BV>
-__device__ __forceinline__ void ss_bf3_split(const FV& v, BV& hi, BV& mid, BV& lo) {
-    bf3_split_pk(v, hi, mid, lo);
-}
-
 constexpr int kSSUnits = RAVE_STACK_UNITS;
 
 #ifdef RAVE_STAMPS
@@ -53,17 +47,6 @@ constexpr int kSSUnits = RAVE_STACK_UNITS;
 // 0 start, 1 window staged, 2/3/4 after unit 0/1/2 (running sums in registers),
 // 5 after the stores, 7 wall clock at the start
 __device__ unsigned long long* g_ss_stamps = nullptr;
-#define SS_STAMP(k)                                                                            \
-    do {                                                                                       \
-        if (threadIdx.x == 0 && g_ss_stamps) {                                                 \
-            g_ss_stamps[blockIdx.x * 8 + (k)] = __builtin_amdgcn_s_memtime();                  \
-            if ((k) == 0) g_ss_stamps[blockIdx.x * 8 + 7] = __builtin_amdgcn_s_memrealtime();  \
-        }                                                                                      \
-    } while (0)
-#else
-#define SS_STAMP(k) \
-    do {            \
-    } while (0)
 #endif
 constexpr unsigned kSSOOB = 0xFFFFFFF0u;
 constexpr int kSSBfHalo = kStackBf3Halo;
@@ -82,25 +65,6 @@ struct SSArgs {
     int d[kSSUnits], pad[kSSUnits];
     float slope;
 };
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t ss_rsrc(const void* p, int bytes) {
-    const uint64_t v = reinterpret_cast<uint64_t>(p);
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v);
-    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
-    const uint64_t u = ((uint64_t)hi << 32) | lo;
-    return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(u), (short)0,
-                                             __builtin_amdgcn_readfirstlane(bytes), 0x00020000);
-}
-
-template <bool SNAKE>
-__device__ __forceinline__ float ss_act(float v, float slope, float alpha) {
-    if constexpr (SNAKE) {
-        const float r = 1.0f / (alpha + 1e-9f);
-        return v + r * sin_squared(alpha * v);
-    } else {
-        return fmaxf(v, v * slope);         // leaky ReLU for slope <= 1 (host check); slope 1 == none
-    }
-}
 
 // C channels (C/32 waves along rows, one 32-row block each); NB centre blocks
 // of 32 columns + 2 margin blocks, CB blocks per wave; NP operand planes (2:
@@ -140,7 +104,7 @@ template <int C, int NB, int CB, bool SNAKE, bool GUARD, bool BF = false, int WX
 __device__ __forceinline__ bool stack_split_body(const SSArgs& a) {
     constexpr int NPW = BF ? 3 : 2;                    // operand planes / weight fragments per K-step
     using G = SSGeo<C, NB, CB, NPW, WX>;
-    constexpr bool GV = GUARD && !BF && RAVE_SPLIT_GUARD != 0;
+    constexpr bool GV = GUARD && !BF;
     constexpr int NT = G::NT, PH = G::PH, XR = G::XR, G8 = G::G8, XT = G::XT, R = G::R;
     constexpr int S1 = G::S1, ST = G::ST, CG = G::CG, OFF = G::OFF;
     extern __shared__ __attribute__((aligned(16))) char lds[];
@@ -152,22 +116,18 @@ __device__ __forceinline__ bool stack_split_body(const SSArgs& a) {
     float* vred = reinterpret_cast<float*>(lds + G::VRED);
 
     const int tid = threadIdx.x;
-    SS_STAMP(0);
+    RAVE_STAMP(g_ss_stamps, 0);
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave % G::WGM, wn = wave / G::WGM;
     const int hh = lane >> 5, l32 = lane & 31;
-#ifdef RAVE_STACK_XCD_MAP
-    const int lg = __builtin_amdgcn_readfirstlane(xcd_major(blockIdx.x, gridDim.x));
-#else
     const int lg = blockIdx.x;      // measured: the stack runs ~1 us slower XCD-major
-#endif
     const int b = lg / a.ntiles;
     const int n0 = (lg - b * a.ntiles) * G::BN;
     const int ext0 = n0 - 32;                       // absolute column of extended column 0
     const int r0 = ext0 - OFF;                      // absolute column of plane row 0
     const float slope = a.act == RAVE_ACT_LEAKY ? a.slope : 1.0f;
-    const auto xrs = ss_rsrc(a.x + (int64_t)b * a.x_sb, a.x_bytes);
+    const auto xrs = make_rsrc(a.x + (int64_t)b * a.x_sb, a.x_bytes);
 
     // ------------------------------------------------------------ per-unit row tables -> LDS
     // (every load in flight at once: a rolled loop waits out one round trip per pass)
@@ -196,7 +156,7 @@ __device__ __forceinline__ bool stack_split_body(const SSArgs& a) {
     const unsigned abase = (unsigned)(wm * ST * NPW) * 1024u + (unsigned)lane * 16u;
     auto wrs_of = [&](int u) __attribute__((always_inline)) {
         const float* w = u == 0 ? a.w[0] : u == 1 ? a.w[1] : a.w[2];
-        return ss_rsrc(w, u < kSSUnits ? a.w_bytes : 0);
+        return make_rsrc(w, u < kSSUnits ? a.w_bytes : 0);
     };
     // step s of the current unit; s >= ST: step s - ST of the next unit
     auto load_a = [&](int slot, __amdgpu_buffer_rsrc_t cur, __amdgpu_buffer_rsrc_t nxt, int s)
@@ -241,11 +201,11 @@ __device__ __forceinline__ bool stack_split_body(const SSArgs& a) {
 #pragma unroll
             for (int v = 0; v < 8; ++v) {
                 const float al = SNAKE ? tab[5 * C + min(g * 8 + v, C - 1)] : 0.f;
-                v8[v] = ok ? ss_act<SNAKE>(rx[i][v], slope, al) * xs : 0.f;
+                v8[v] = ok ? act<SNAKE>(rx[i][v], slope, al) * xs : 0.f;
             }
             if constexpr (BF) {
                 ss_b8 hi, mid, lo;
-                ss_bf3_split(v8, hi, mid, lo);
+                bf3_split_pk(v8, hi, mid, lo);
                 if (e < XR * G8) {
                     *reinterpret_cast<ss_b8*>(ph + w * PH + g * 8) = hi;
                     *reinterpret_cast<ss_b8*>(pl + w * PH + g * 8) = lo;
@@ -311,7 +271,7 @@ __device__ __forceinline__ bool stack_split_body(const SSArgs& a) {
                     const int c = min(g * 8 + v, C - 1);
                     const float xv = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
                         xrs, (unsigned)(c * a.x_sc + t) * 4u, 0, 0));
-                    v8[v] = ok ? ss_act<SNAKE>(xv, slope, SNAKE ? tab[5 * C + c] : 0.f) * xs : 0.f;
+                    v8[v] = ok ? act<SNAKE>(xv, slope, SNAKE ? tab[5 * C + c] : 0.f) * xs : 0.f;
                 }
                 const ss_h8 hi = __builtin_convertvector(v8, ss_h8);
                 const ss_h8 lo = __builtin_convertvector((v8 - __builtin_convertvector(hi, ss_f32x8)) * 2048.0f, ss_h8);
@@ -322,7 +282,7 @@ __device__ __forceinline__ bool stack_split_body(const SSArgs& a) {
         }
     }
 
-    SS_STAMP(1);
+    RAVE_STAMP(g_ss_stamps, 1);
     struct BFr {
         ss_h8 h[CB], l[CB], m[BF ? CB : 1];
     };
@@ -361,10 +321,10 @@ __device__ __forceinline__ bool stack_split_body(const SSArgs& a) {
                 const bool ok = !mask || (t >= 0 && t < a.T);
                 ss_f32x4 w4;
 #pragma unroll
-                for (int e = 0; e < 4; ++e) w4[e] = ok ? ss_act<SNAKE>(v[j][4 * g + e], slope, al[e]) * xs : 0.f;
+                for (int e = 0; e < 4; ++e) w4[e] = ok ? act<SNAKE>(v[j][4 * g + e], slope, al[e]) * xs : 0.f;
                 if constexpr (BF) {
                     ss_b4 hi, mid, lo;
-                    ss_bf3_split(w4, hi, mid, lo);
+                    bf3_split_pk(w4, hi, mid, lo);
                     *reinterpret_cast<ss_b4*>(ph + (OFF + col0 + 32 * j) * PH + m) = hi;
                     *reinterpret_cast<ss_b4*>(pl + (OFF + col0 + 32 * j) * PH + m) = lo;
                     *reinterpret_cast<ss_b4*>(pm + (OFF + col0 + 32 * j) * PH + m) = mid;
@@ -490,7 +450,7 @@ __device__ __forceinline__ bool stack_split_body(const SSArgs& a) {
                     yv[j][4 * g + e] = acc[j][4 * g + e] * rs[e] + bb[e] + yv[j][4 * g + e];
         }
         zero_acc();
-        SS_STAMP(2 + u);
+        RAVE_STAMP(g_ss_stamps, 2 + u);
         if (u + 1 < kSSUnits) {
             __syncthreads();                           // h dead
             sh0 = guarded_planes(yv, tu + 6 * C + 5 * C, true);    // next unit's act0(y)
@@ -499,7 +459,7 @@ __device__ __forceinline__ bool stack_split_body(const SSArgs& a) {
 
     // unguarded pass: a non-finite centre sum -> run again guarded (flag here,
     // workgroup vote after the stores, which the guarded pass rewrites)
-    constexpr bool CHECK = !GUARD && !BF && RAVE_SPLIT_GUARD != 0;
+    constexpr bool CHECK = !GUARD && !BF;
     bool bad = false;
     if constexpr (CHECK) {
 #pragma unroll
@@ -511,7 +471,7 @@ __device__ __forceinline__ bool stack_split_body(const SSArgs& a) {
         }
     }
     // ------------------------------------------------------------ centre blocks -> y
-    const auto yrs = ss_rsrc(a.y + (int64_t)b * a.y_sb, a.y_bytes);
+    const auto yrs = make_rsrc(a.y + (int64_t)b * a.y_sb, a.y_bytes);
 #pragma unroll
     for (int j = 0; j < CB; ++j) {
         if (VAR && j >= nbw) break;
@@ -522,10 +482,10 @@ __device__ __forceinline__ bool stack_split_body(const SSArgs& a) {
         for (int r = 0; r < 16; ++r) {
             const int m = mrow0 + 8 * (r >> 2) + (r & 3);
             __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, yv[j][r]), yrs,
-                                                  ok ? (unsigned)(m * a.y_sc + t) * 4u : kSSOOB, 0, RAVE_YAUX);
+                                                  ok ? (unsigned)(m * a.y_sc + t) * 4u : kSSOOB, 0, 0);
         }
     }
-    SS_STAMP(5);
+    RAVE_STAMP(g_ss_stamps, 5);
     if constexpr (CHECK) {
         vote_cast_any(vote, wave, bad);
         __syncthreads();
@@ -539,7 +499,7 @@ __device__ __forceinline__ bool stack_split_body(const SSArgs& a) {
 
 template <int C, int NB, int CB, bool SNAKE>
 __global__ __launch_bounds__(64 * (C / 32) * ((NB + 2) / CB)) void stack_split_kernel(SSArgs a) {
-    if (!stack_split_body<C, NB, CB, SNAKE, RAVE_SPLIT_GUARD == 0>(a)) (void)stack_split_body<C, NB, CB, SNAKE, true>(a);
+    if (!stack_split_body<C, NB, CB, SNAKE, false>(a)) (void)stack_split_body<C, NB, CB, SNAKE, true>(a);
 }
 template <int C, int NB, int CB, bool SNAKE, int WX>
 __global__ __launch_bounds__((SSGeo<C, NB, CB, 3, WX>::NT)) void stack_bf3_kernel(SSArgs a) {

@@ -39,6 +39,7 @@
 // sets the workspace's RAVE_SPLITK_STATUS_WORD (sticky), which the owner of the
 // workspace reads back and reports (the engine returns RAVE_ERR_COOP).
 #include "common.h"
+#include "pack_shared.h"
 
 #include <algorithm>
 #include <atomic>
@@ -58,17 +59,7 @@ typedef unsigned us_u32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 us_b8 __attribute__((ext_vector_type(8)));
 typedef __bf16 us_b4 __attribute__((ext_vector_type(4)));
 
-// fp32 -> three bf16 parts with v == hi + mid + lo exactly (8 + 8 + 8 bits of
-// the 24-bit significand; each remainder is exact in fp32)
-template <typename FV, typename BV>
-__device__ __forceinline__ void bf3_split(const FV& v, BV& hi, BV& mid, BV& lo) {
-    bf3_split_pk(v, hi, mid, lo);
-}
-
 constexpr int kUSMaxDil = 16;
-#ifndef RAVE_COOP_SC1
-#define RAVE_COOP_SC1 1
-#endif
 #ifndef RAVE_US_R
 #define RAVE_US_R 3
 #endif
@@ -76,37 +67,22 @@ constexpr int kUSMaxDil = 16;
 #define RAVE_US_RC 6                // weight ring depth of the cooperative form (4 waves per CU)
 #endif
 constexpr unsigned kUSSpinLimit = 1u << 18;   // cooperative seam: bounded poll (give-up -> status word + NaN)
-template <int V> struct IC {
-    static constexpr int value = V;
-};
-
 #ifdef RAVE_STAMPS
 // diagnostic build only: 8 clock stamps per workgroup (tools/layer_bench.py --stamps)
 __device__ unsigned long long* g_us_stamps = nullptr;
-#define US_STAMP(k)                                                                            \
-    do {                                                                                       \
-        if (threadIdx.x == 0 && g_us_stamps) {                                                 \
-            g_us_stamps[blockIdx.x * 8 + (k)] = __builtin_amdgcn_s_memtime();                  \
-            if ((k) == 0) g_us_stamps[blockIdx.x * 8 + 7] = __builtin_amdgcn_s_memrealtime();  \
-        }                                                                                      \
-    } while (0)
-#else
-#define US_STAMP(k) \
-    do {            \
-    } while (0)
 #endif
 // US_AT(k, kc): stamp slot k in the diagnostic build, slot kc in the cooperative-detail
 // one (-DRAVE_STAMPS_COOP: 0 start, 1 window staged, 2 phase 1, 3 published, 4 own
 // phase-2 steps done, 5 poll done, 6 partner rows staged); -1 = no stamp there
 #ifdef RAVE_STAMPS_COOP
-#define US_AT(k, kc)                \
-    do {                            \
-        if ((kc) >= 0) US_STAMP(kc); \
+#define US_AT(k, kc)                                 \
+    do {                                             \
+        if ((kc) >= 0) RAVE_STAMP(g_us_stamps, kc); \
     } while (0)
 #else
-#define US_AT(k, kc)               \
-    do {                           \
-        if ((k) >= 0) US_STAMP(k); \
+#define US_AT(k, kc)                               \
+    do {                                           \
+        if ((k) >= 0) RAVE_STAMP(g_us_stamps, k); \
     } while (0)
 #endif
 constexpr unsigned kUSOOB = 0xFFFFFFF0u;
@@ -135,25 +111,6 @@ struct USArgs {
     unsigned spin_limit;     // polls before a member gives up (rave_debug_coop)
     int force_giveup;        // debug: every group reports a give-up after a normal hand-off
 };
-
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t us_rsrc(const void* p, int bytes) {
-    const uint64_t v = reinterpret_cast<uint64_t>(p);
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v);
-    const uint32_t hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
-    const uint64_t u = ((uint64_t)hi << 32) | lo;
-    return __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void*>(u), (short)0,
-                                             __builtin_amdgcn_readfirstlane(bytes), 0x00020000);
-}
-
-template <bool SNAKE>
-__device__ __forceinline__ float us_act(float v, float slope, float alpha) {
-    if constexpr (SNAKE) {
-        const float r = 1.0f / (alpha + 1e-9f);
-        return v + r * sin_squared(alpha * v);
-    } else {
-        return fmaxf(v, v * slope);         // leaky ReLU for slope <= 1 (host check); slope 1 == none
-    }
-}
 
 // C channels; WGN waves along time (each 64 columns); C/(32 MI) waves along
 // rows (each MI 32-row blocks).
@@ -217,7 +174,7 @@ __device__ __forceinline__ bool unit_split_body(const USArgs& a) {
     using G = USGeo<C, WGN, MI, KG, CB, RB, NPW>;
     // cooperative form with one workgroup per CU (its LDS rules out a second):
     // the hand-off reads the exchange by sc1 loads instead of an agent acquire
-    // (RAVE_COOP_SC1=0 keeps the acquire: A/B).  What this rests on is the
+    // (measured against keeping the acquire).  What this rests on is the
     // guide's measured form (MI355X_MICROARCH.md, Valid forms, Consumer bullet
     // (1)-(4), hand-off table row 1), every condition of which holds here:
     // every byte of the exchange is stored sc1 (the seam's publish) and read
@@ -230,9 +187,9 @@ __device__ __forceinline__ bool unit_split_body(const USArgs& a) {
     // is for speed (the exchange stays in one L2) and for residency, not for
     // visibility.  Forms with two workgroups per CU (split16 C = 256) keep the
     // agent acquire, so both paths stay covered by the cooperative tests.
-    constexpr bool SC1X = RB > 1 && RAVE_COOP_SC1 != 0 && 2 * G::LDS > 160 * 1024;
+    constexpr bool SC1X = RB > 1 && 2 * G::LDS > 160 * 1024;
     static_assert(!SC1X || 2 * G::LDS > 160 * 1024, "sc1 hand-off: one workgroup per CU only");
-    constexpr bool GV = GUARD && AR == 0 && RAVE_SPLIT_GUARD != 0;   // votes inside the body
+    constexpr bool GV = GUARD && AR == 0;   // votes inside the body
     static_assert(RB == 1 || GUARD || AR != 0, "the cooperative split16 form runs guarded");
     constexpr int NT = G::NT, PH = G::PH, G8 = G::G8, XT = G::XT, R = G::R;
     constexpr int S1 = G::S1, ST = G::ST, CG = C / 16;
@@ -271,8 +228,8 @@ __device__ __forceinline__ bool unit_split_body(const USArgs& a) {
     const int ntask = XW * G8;
     const int t0 = n0 - a.pad_l;
 
-    const auto xrs = us_rsrc(a.x + (int64_t)b * a.x_sb, a.x_bytes);
-    const auto wrs = us_rsrc(a.w, a.w_bytes);
+    const auto xrs = make_rsrc(a.x + (int64_t)b * a.x_sb, a.x_bytes);
+    const auto wrs = make_rsrc(a.w, a.w_bytes);
     int sh0 = 0, sh2 = 0;                            // range-guard shifts of the two GEMMs' B operands
 
     // ------------------------------------------------------------ weight ring
@@ -348,7 +305,7 @@ __device__ __forceinline__ bool unit_split_body(const USArgs& a) {
 #pragma unroll
             for (int v = 0; v < 8; ++v) {
                 const float al = SNAKE ? a.a0[min(g * 8 + v, C - 1)] : 0.f;   // L1-hot
-                v8[v] = ok ? us_act<SNAKE>(rx[i][v], slope, al) * xs : 0.f;
+                v8[v] = ok ? act<SNAKE>(rx[i][v], slope, al) * xs : 0.f;
             }
             if constexpr (F32) {
                 if (e < ntask) {
@@ -357,7 +314,7 @@ __device__ __forceinline__ bool unit_split_body(const USArgs& a) {
                 }
             } else if constexpr (BF) {
                 us_b8 hi, mid, lo;
-                bf3_split(v8, hi, mid, lo);
+                bf3_split_pk(v8, hi, mid, lo);
                 if (e < ntask) {
                     *reinterpret_cast<us_b8*>(ph + w * PH + g * 8) = hi;
                     *reinterpret_cast<us_b8*>(pl + w * PH + g * 8) = lo;
@@ -396,14 +353,8 @@ __device__ __forceinline__ bool unit_split_body(const USArgs& a) {
             const bool ok = (e < ntv) && t >= 0 && t < a.XL;
 #pragma unroll
             for (int v = 0; v < 8; ++v) {
-#ifdef RAVE_EXP_NOWIN
-                // timing-only A/B variant (wrong results, never shipped): no window
-                // loads -- bounds what hiding the prologue's loads could buy
-                rx[i][v] = us_f32x4{0.01f * v, 0.02f * i, ok ? 0.5f : 0.f, 0.25f};
-#else
                 rx[i][v] = __builtin_bit_cast(us_f32x4, __builtin_amdgcn_raw_buffer_load_b128(
                     xrs, ok ? (unsigned)((g * 8 + v) * a.x_sc + t) * 4u : kUSOOB, 0, 0));
-#endif
             }
         }
         prefetch_ring();
@@ -426,14 +377,14 @@ __device__ __forceinline__ bool unit_split_body(const USArgs& a) {
                     const int w = ta + 4 * kb + q - t0;
                     us_f32x8 v8;
 #pragma unroll
-                    for (int v = 0; v < 8; ++v) v8[v] = us_act<SNAKE>(rx[i][v][q], slope, al[v]);
+                    for (int v = 0; v < 8; ++v) v8[v] = act<SNAKE>(rx[i][v][q], slope, al[v]);
                     if (w < 0 || w >= XW) continue;
                     if constexpr (F32) {
                         *reinterpret_cast<us_f32x4*>(pf + w * PH + g * 8) = us_f32x4{v8[0], v8[1], v8[2], v8[3]};
                         *reinterpret_cast<us_f32x4*>(pf + w * PH + g * 8 + 4) = us_f32x4{v8[4], v8[5], v8[6], v8[7]};
                     } else if constexpr (BF) {
                         us_b8 hi, mid, lo;
-                        bf3_split(v8, hi, mid, lo);
+                        bf3_split_pk(v8, hi, mid, lo);
                         *reinterpret_cast<us_b8*>(ph + w * PH + g * 8) = hi;
                         *reinterpret_cast<us_b8*>(pl + w * PH + g * 8) = lo;
                         *reinterpret_cast<us_b8*>(pm + w * PH + g * 8) = mid;
@@ -477,7 +428,7 @@ __device__ __forceinline__ bool unit_split_body(const USArgs& a) {
                     const int c = min(g * 8 + v, C - 1);
                     const float xv = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
                         xrs, (unsigned)(c * a.x_sc + t) * 4u, 0, 0));
-                    v8[v] = ok ? us_act<SNAKE>(xv, slope, SNAKE ? a.a0[c] : 0.f) * xs : 0.f;
+                    v8[v] = ok ? act<SNAKE>(xv, slope, SNAKE ? a.a0[c] : 0.f) * xs : 0.f;
                 }
                 const us_h8 hi = __builtin_convertvector(v8, us_h8);
                 const us_h8 lo = __builtin_convertvector((v8 - __builtin_convertvector(hi, us_f32x8)) * 2048.0f, us_h8);
@@ -666,7 +617,7 @@ __device__ __forceinline__ bool unit_split_body(const USArgs& a) {
     // range guard's scale of h; returns max |h xs| of the thread's values)
     const float f0 = ldexpf(1.0f, sh0);
     // cooperative form: this group's exchange slot (act2(h) as [BN columns][C] fp32)
-    const auto xcrs = us_rsrc(a.xch, RB > 1 ? a.xch_bytes : 0);
+    const auto xcrs = make_rsrc(a.xch, RB > 1 ? a.xch_bytes : 0);
     const unsigned xslot = (unsigned)lg * (unsigned)(G::BN * C);
     auto seam = [&](float xs, auto pubtag) __attribute__((always_inline)) {
         constexpr bool publish = decltype(pubtag)::value != 0 && RB > 1;
@@ -686,7 +637,7 @@ __device__ __forceinline__ bool unit_split_body(const USArgs& a) {
                         us_f32x4 v;
 #pragma unroll
                         for (int e = 0; e < 4; ++e)
-                            v[e] = us_act<SNAKE>(acc[i][j][4 * g + e] * rs[e] + bb[e], slope, al[e]) * xs;
+                            v[e] = act<SNAKE>(acc[i][j][4 * g + e] * rs[e] + bb[e], slope, al[e]) * xs;
                         if constexpr (publish)   // write-through (sc1): read by the other members
                             __builtin_amdgcn_raw_buffer_store_b128(
                                 __builtin_bit_cast(us_u32x4, v), xcrs,
@@ -697,7 +648,7 @@ __device__ __forceinline__ bool unit_split_body(const USArgs& a) {
                         }
                         if constexpr (BF) {
                             us_b4 hi, mid, lo;
-                            bf3_split(v, hi, mid, lo);
+                            bf3_split_pk(v, hi, mid, lo);
                             *reinterpret_cast<us_b4*>(ph + (col0 + 32 * j) * PH + m) = hi;
                             *reinterpret_cast<us_b4*>(pl + (col0 + 32 * j) * PH + m) = lo;
                             *reinterpret_cast<us_b4*>(pm + (col0 + 32 * j) * PH + m) = mid;
@@ -781,7 +732,7 @@ __device__ __forceinline__ bool unit_split_body(const USArgs& a) {
         for (int r = 0; r < RB; ++r)
             gmax = fmaxf(gmax, __builtin_bit_cast(float, __hip_atomic_load(reinterpret_cast<unsigned*>(a.xmax) + lg * RB + r,
                                                                             __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)));
-        if constexpr (AR == 0) sh2 = __builtin_amdgcn_readfirstlane((RAVE_SPLIT_GUARD && gmax >= kSplitLimit) ? split_shift(gmax) : 0);
+        if constexpr (AR == 0) sh2 = __builtin_amdgcn_readfirstlane((gmax >= kSplitLimit) ? split_shift(gmax) : 0);
         // stage the other members' rows (all rows, scaled, on the rare guarded path)
         auto stage_rows = [&](auto alltag, float xs) __attribute__((always_inline)) {
             constexpr bool all = decltype(alltag)::value != 0;
@@ -818,7 +769,7 @@ __device__ __forceinline__ bool unit_split_body(const USArgs& a) {
                     const us_f32x8 v8 = us_f32x8{v0[i][0], v0[i][1], v0[i][2], v0[i][3],
                                                  v1[i][0], v1[i][1], v1[i][2], v1[i][3]};
                     us_b8 hi, mid, lo;
-                    bf3_split(v8, hi, mid, lo);
+                    bf3_split_pk(v8, hi, mid, lo);
                     *reinterpret_cast<us_b8*>(ph + w * PH + g * 8) = hi;
                     *reinterpret_cast<us_b8*>(pl + w * PH + g * 8) = lo;
                     *reinterpret_cast<us_b8*>(pm + w * PH + g * 8) = mid;
@@ -871,7 +822,7 @@ __device__ __forceinline__ bool unit_split_body(const USArgs& a) {
     // guarded.  The flag is taken here; the workgroup vote follows the epilogue's
     // stores (KG == 1: the second pass rewrites them; a barrier there costs no
     // wave anything), or comes here (KG == 2: the partner waves leave below)
-    constexpr bool CHECK = !GUARD && AR == 0 && RAVE_SPLIT_GUARD != 0;
+    constexpr bool CHECK = !GUARD && AR == 0;
     bool bad = false;
     if constexpr (CHECK) {
         if (KG == 1 || kg == 0) {
@@ -904,7 +855,7 @@ __device__ __forceinline__ bool unit_split_body(const USArgs& a) {
     // every residual load issued before the first store (one exposed latency)
     {
         const float f2 = ldexpf(1.0f, sh2);
-        const auto yrs = us_rsrc(a.y + (int64_t)b * a.y_sb, a.y_bytes);
+        const auto yrs = make_rsrc(a.y + (int64_t)b * a.y_sb, a.y_bytes);
         float res[MI][CB][16];
 #pragma unroll
         for (int j = 0; j < CB; ++j) {
@@ -935,7 +886,7 @@ __device__ __forceinline__ bool unit_split_body(const USArgs& a) {
                         __builtin_amdgcn_raw_buffer_store_b32(
                             __builtin_bit_cast(unsigned, gave_up ? __builtin_nanf("")
                                                                  : acc[i][j][4 * g + e] * rs[e] + bb[e] + res[i][j][4 * g + e]),
-                            yrs, nok ? (unsigned)((m + e) * a.y_sc + n) * 4u : kUSOOB, 0, RAVE_YAUX);
+                            yrs, nok ? (unsigned)((m + e) * a.y_sc + n) * 4u : kUSOOB, 0, 0);
                 }
             }
     }
@@ -948,7 +899,7 @@ __device__ __forceinline__ bool unit_split_body(const USArgs& a) {
 
 template <int C, int WGN, int MI, int KG, int CB, bool SNAKE, int RB>
 __global__ __launch_bounds__(64 * (C / (32 * MI * RB)) * WGN * KG) void unit_split_kernel(USArgs a) {
-    if constexpr (RB > 1 || RAVE_SPLIT_GUARD == 0) {
+    if constexpr (RB > 1) {
         (void)unit_split_body<C, WGN, MI, KG, CB, SNAKE, 0, RB, true>(a);
     } else {
         if (!unit_split_body<C, WGN, MI, KG, CB, SNAKE, 0, RB, false>(a))
@@ -1052,46 +1003,22 @@ static int us_launch(USArgs k, int B, bool snake, int ar, hipStream_t st) {
 
 static bool us_supported(int C) { return C == 64 || C == 128 || C == 256 || C == 512; }
 
-// Power-of-two row exponent: max |w * 2^e| in [8, 16) (e = 0 for an all-zero row).
-static int us_row_exponent(double amax) {
-    if (!(amax > 0.0)) return 0;
-    int e = (int)std::floor(std::log2(16.0 / amax));
-    while (std::ldexp(amax, e) >= 16.0) --e;
-    while (std::ldexp(amax, e) < 8.0) ++e;
-    return e;
-}
-
-
 }  // namespace rave
 
 using namespace rave;
 
-// packed: fragments [C/32 m-blocks][S1+S2 K-steps][hi, lo][64 lanes][8 halves], then
-// rs1[C], rs2[C] (floats).  Sizes in floats.
-extern "C" int64_t rave_unit_split_packed_size(int C) {
+// packed: fragments [C/32 m-blocks][S1+S2 K-steps][planes][64 lanes][8 values] (split16
+// and fp32: hi, lo; bf16x3: hi, lo, mid), then rs1[C], rs2[C] (floats).  Sizes in floats.
+static int64_t unit_packed_floats(int C, int planes) {
     if (!us_supported(C)) return -1;
-    const int ST = 4 * C / 16;
-    return (int64_t)(C / 32) * ST * 2 * 256 + 2 * C;
+    return packed_floats((int64_t)(C / 32) * (4 * C / 16), planes, 2 * C);
 }
+extern "C" int64_t rave_unit_split_packed_size(int C) { return unit_packed_floats(C, 2); }
+extern "C" int64_t rave_unit_bf3_packed_size(int C) { return unit_packed_floats(C, 3); }
 
-// host fp32 -> bf16, round to nearest even (finite weights)
-static uint16_t bf16_bits(float f) {
-    uint32_t u;
-    std::memcpy(&u, &f, 4);
-    u += 0x7FFFu + ((u >> 16) & 1u);
-    return (uint16_t)(u >> 16);
-}
-static float bf16_value(uint16_t h) {
-    const uint32_t u = (uint32_t)h << 16;
-    float f;
-    std::memcpy(&f, &u, 4);
-    return f;
-}
-
-// mode: 0 split16 (hi, lo f16, row scales), 1 exact fp32, 2 bf16x3 (hi, lo, mid)
+// mode (PackMode): split16 (hi, lo f16, row scales), exact fp32, bf16x3 (hi, lo, mid)
 static int unit_pack(const float* w1, const float* w2, int C, float* packed, int mode) {
-    const bool f32 = mode != 0;                      // (no row scales)
-    const int NPW = mode == 2 ? 3 : 2;
+    const bool f32 = mode != kPackSplit16;           // (no row scales)
     RAVE_CHECK_ARG(w1 && w2 && packed, "unit_split_pack_weight: null pointer");
     if (!us_supported(C)) {
         set_error("unit_split_pack_weight: split16 fused residual unit supports C in {64, 128, 256, 512}");
@@ -1103,17 +1030,13 @@ static int unit_pack(const float* w1, const float* w2, int C, float* packed, int
         double a1 = 0.0, a2 = 0.0;
         for (int k = 0; k < 3 * C; ++k) a1 = std::max(a1, (double)std::fabs(w1[(int64_t)m * 3 * C + k]));
         for (int k = 0; k < C; ++k) a2 = std::max(a2, (double)std::fabs(w2[(int64_t)m * C + k]));
-        e1[m] = f32 ? 0 : us_row_exponent(a1);
-        e2[m] = f32 ? 0 : us_row_exponent(a2);
+        e1[m] = f32 ? 0 : row_exponent(a1);
+        e2[m] = f32 ? 0 : row_exponent(a2);
     }
-    _Float16* out = reinterpret_cast<_Float16*>(packed);
-    uint16_t* bout = reinterpret_cast<uint16_t*>(packed);
+    // fragment (32-row block mb, K-step s): lane l holds row l & 31, element e
+    // input channel 8 (l >> 5) + e of the step's 16
     for (int mb = 0; mb < C / 32; ++mb)
-        for (int s = 0; s < ST; ++s) {
-            uint16_t* bp = bout + ((int64_t)(mb * ST + s) * 3) * 512;   // bf16x3: hi, lo, mid
-            _Float16* hi = out + ((int64_t)(mb * ST + s) * 2) * 512;
-            _Float16* lo = hi + 512;
-            float* f32s = packed + ((int64_t)(mb * ST + s) * 2) * 256;   // fp32: floats 0-3 slot 0, 4-7 slot 1
+        for (int s = 0; s < ST; ++s)
             for (int l = 0; l < 64; ++l)
                 for (int e = 0; e < 8; ++e) {
                     const int m = mb * 32 + (l & 31);
@@ -1126,25 +1049,9 @@ static int unit_pack(const float* w1, const float* w2, int C, float* packed, int
                         const int ci = (s - S1) * 16 + kk;
                         v = std::ldexp(w2[(int64_t)m * C + ci], e2[m]);
                     }
-                    if (mode == 2) {
-                        const uint16_t h = bf16_bits(v);
-                        const float r = v - bf16_value(h);
-                        const uint16_t md = bf16_bits(r);
-                        bp[l * 8 + e] = h;
-                        bp[1024 + l * 8 + e] = md;
-                        bp[512 + l * 8 + e] = bf16_bits(r - bf16_value(md));
-                        continue;
-                    }
-                    if (f32) {
-                        f32s[(e >> 2) * 256 + l * 4 + (e & 3)] = v;
-                        continue;
-                    }
-                    const _Float16 vh = (_Float16)v;
-                    hi[l * 8 + e] = vh;
-                    lo[l * 8 + e] = (_Float16)((v - (float)vh) * 2048.0f);
+                    put_fragment(packed, (int64_t)mb * ST + s, mode, l, e, v);
                 }
-        }
-    float* rs = packed + (int64_t)(C / 32) * ST * NPW * 256;
+    float* rs = packed + packed_floats((int64_t)(C / 32) * ST, pack_planes(mode), 0);
     for (int m = 0; m < C; ++m) {
         rs[m] = f32 ? 1.0f : (float)std::ldexp(1.0, -(e1[m] + 11));
         rs[C + m] = f32 ? 1.0f : (float)std::ldexp(1.0, -(e2[m] + 11));
@@ -1153,22 +1060,15 @@ static int unit_pack(const float* w1, const float* w2, int C, float* packed, int
 }
 
 extern "C" int rave_unit_split_pack_weight(const float* w1, const float* w2, int C, float* packed) {
-    return unit_pack(w1, w2, C, packed, 0);
+    return unit_pack(w1, w2, C, packed, kPackSplit16);
 }
 
 extern "C" int rave_unit_ring_pack_weight(const float* w1, const float* w2, int C, float* packed) {
-    return unit_pack(w1, w2, C, packed, 1);
-}
-
-// bf16x3: fragments [C/32][S1+S2][hi, lo, mid][64 lanes][8 bf16], then rs1, rs2 (= 1)
-extern "C" int64_t rave_unit_bf3_packed_size(int C) {
-    if (!us_supported(C)) return -1;
-    const int ST = 4 * C / 16;
-    return (int64_t)(C / 32) * ST * 3 * 256 + 2 * C;
+    return unit_pack(w1, w2, C, packed, kPackF32);
 }
 
 extern "C" int rave_unit_bf3_pack_weight(const float* w1, const float* w2, int C, float* packed) {
-    return unit_pack(w1, w2, C, packed, 2);
+    return unit_pack(w1, w2, C, packed, kPackBf16x3);
 }
 
 #ifdef RAVE_STAMPS
