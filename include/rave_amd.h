@@ -27,6 +27,9 @@
  *                        autograd's backward through those two, as the training
  *                        step needs it between the decoder and the spectral loss
  *                        (rave/model.py:358-391).
+ *   rave_noise_synth_backward / rave_adain_backward
+ *                        autograd's backward through NoiseGeneratorV2's filter stage
+ *                        (to the band amplitudes) and through eval-mode AdaIN (to x).
  *   rave_fill_channels  the speaker-embedding concat of RAVE.encode
  *                        rave/model.py:618-620.
  *   rave_rvq_encode /    ResidualVectorQuantization.encode / decode
@@ -464,6 +467,28 @@ typedef struct rave_noise_args {
 } rave_noise_args;
 int rave_noise_synth(const rave_noise_args* a, void* stream);
 
+/* The gradient of rave_noise_synth with respect to amp (the draw u is a constant, as the
+ * reference's torch.rand_like is).  With fs = 2*(noise_bands-1), v = 2u - 1, win the
+ * periodic Hann window of length fs and s_k = sigmoid(amp[b, j*noise_bands + k, f] - 5),
+ * for every (b, frame f, band j):
+ *   gh[n]  = sum_{i=n}^{target-1} gy[b, j, f*target + i] * v[b, f, j, i - n]   (the fs live taps)
+ *   gir[n] = gh[n] * win[n + fs/2]                    n <  fs/2
+ *   gir[m] = gh[m + target - fs] * win[m - fs/2]      fs/2 <= m < fs
+ *   gA_k   = (c_k / fs) * sum_{n<fs} gir[n] * cos(2 pi k n / fs)     c_0 = c_last = 1, else 2
+ *   gamp[b, j*noise_bands + k, f] = gA_k * 4.6 * s_k^2.3 * (1 - s_k)
+ * with 1 - s_k evaluated as sigmoid(5 - amp).  One launch, no atomics and no workspace:
+ * two calls give the same bits.  The forward's shapes and refusals; amp, u as the forward
+ * read them; gy / gamp time (frame) contiguous. */
+typedef struct rave_noise_backward_args {
+    int32_t batch, frames, n_band, noise_bands;
+    int32_t target, _pad0;
+    const float* amp; int64_t a_sb, a_sc;     /* (B, n_band*noise_bands, frames) */
+    const float* u;   int64_t u_sb;
+    const float* gy;  int64_t gy_sb, gy_sc;   /* (B, n_band, frames*target)      */
+    float* gamp;      int64_t ga_sb, ga_sc;   /* (B, n_band*noise_bands, frames) */
+} rave_noise_backward_args;
+int rave_noise_synth_backward(const rave_noise_backward_args* a, void* stream);
+
 /* ---------------------------------------------------------------- AdaIN
  * AdaptiveInstanceNormalization.forward in eval mode (rave/blocks.py:856-919) over
  * the module's own buffers, kept on the device:
@@ -488,6 +513,24 @@ typedef struct rave_adain_args {
     uint32_t* ticket;
 } rave_adain_args;
 int rave_adain(const rave_adain_args* a, void* stream);
+
+/* The gradient of rave_adain with respect to x; the statistics are buffers and count as
+ * constants in every mode (mode 1 transfers with the statistics it has just updated):
+ *   gx = gy / (std_x[row] + 1e-5) * std_y[row]    where the forward transferred
+ *   gx = gy                                       where it did not
+ * The kernel decides that itself, by the forward's condition (mode != 2, num_update_x
+ * != 0, num_update_y != 0) on `stats` and `counters` AS THEY STOOD AFTER THE FORWARD
+ * CALL, read on the device: the host never waits for them.  Nothing is written but gx;
+ * gx may alias gy.  Grid and row addressing (row = row0 + b) as the forward's. */
+typedef struct rave_adain_backward_args {
+    int32_t batch, channels, t_len, mode;
+    int32_t max_batch, row0;
+    const float* gy; int64_t gy_sb, gy_sc;
+    float* gx;       int64_t gx_sb, gx_sc;
+    const float* stats;       /* (4, max_batch, channels), after the forward */
+    const float* counters;    /* float[2], after the forward                 */
+} rave_adain_backward_args;
+int rave_adain_backward(const rave_adain_backward_args* a, void* stream);
 
 /* ---------------------------------------------------------------- fused residual unit
  * Residual(DilatedUnit(C, k=3, d)) in one kernel (rave/blocks.py:32-46, 84-113):

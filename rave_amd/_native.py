@@ -165,6 +165,23 @@ class AdainArgs(C.Structure):
                 ("stats", vp), ("counters", vp), ("ticket", vp)]
 
 
+class NoiseBackwardArgs(C.Structure):
+    _fields_ = [("batch", i32), ("frames", i32), ("n_band", i32), ("noise_bands", i32),
+                ("target", i32), ("_pad0", i32),
+                ("amp", vp), ("a_sb", i64), ("a_sc", i64),
+                ("u", vp), ("u_sb", i64),
+                ("gy", vp), ("gy_sb", i64), ("gy_sc", i64),
+                ("gamp", vp), ("ga_sb", i64), ("ga_sc", i64)]
+
+
+class AdainBackwardArgs(C.Structure):
+    _fields_ = [("batch", i32), ("channels", i32), ("t_len", i32), ("mode", i32),
+                ("max_batch", i32), ("row0", i32),
+                ("gy", vp), ("gy_sb", i64), ("gy_sc", i64),
+                ("gx", vp), ("gx_sb", i64), ("gx_sc", i64),
+                ("stats", vp), ("counters", vp)]
+
+
 class UnitArgs(C.Structure):
     _fields_ = [("channels", i32), ("batch", i32), ("t_len", i32), ("dilation", i32),
                 ("pad_left", i32), ("act", i32), ("leaky_slope", f32), ("precision", i32),
@@ -307,7 +324,7 @@ STRUCTS = [ConvArgs, AnalysisArgs, SynthesisArgs, FillArgs, RvqArgs, ShiftArgs, 
            CopyArgs, NoiseArgs, AdainArgs, UnitArgs, StackArgs, ModelConfig, Param, OpInfo,
            FirArgs, RowStatsArgs, AttnPoolArgs, LinearArgs, MaxPoolArgs, EdgeArgs,
            StftArgs, DistanceArgs, YinArgs, F0OneHotArgs, SynthesisBackwardArgs, AnalysisBackwardArgs,
-           ConvBackwardArgs, StftLossArgs]
+           ConvBackwardArgs, NoiseBackwardArgs, AdainBackwardArgs, StftLossArgs]
 
 # every exported symbol of include/rave_amd.h
 EXPORTS = [
@@ -321,6 +338,7 @@ EXPORTS = [
     "rave_pqmf_analysis", "rave_pqmf_synthesis", "rave_pqmf_analysis_backward", "rave_pqmf_synthesis_backward",
     "rave_fill_channels", "rave_copy",
     "rave_rvq_workspace", "rave_rvq_encode", "rave_rvq_decode", "rave_shift_history", "rave_noise_synth", "rave_adain",
+    "rave_noise_synth_backward", "rave_adain_backward",
     "rave_unit_packed_size", "rave_unit_pack_weight", "rave_residual_unit",
     "rave_unit_split_packed_size", "rave_unit_split_pack_weight", "rave_unit_ring_pack_weight",
     "rave_unit_bf3_packed_size", "rave_unit_bf3_pack_weight",
@@ -413,6 +431,7 @@ def _load():
                      ("rave_rvq_encode", RvqArgs), ("rave_rvq_decode", RvqArgs),
                      ("rave_shift_history", ShiftArgs), ("rave_copy", CopyArgs),
                      ("rave_noise_synth", NoiseArgs), ("rave_adain", AdainArgs),
+                     ("rave_noise_synth_backward", NoiseBackwardArgs), ("rave_adain_backward", AdainBackwardArgs),
                      ("rave_residual_unit", UnitArgs), ("rave_residual_stack", StackArgs),
                      ("rave_fir", FirArgs), ("rave_row_stats", RowStatsArgs), ("rave_attn_pool", AttnPoolArgs),
                      ("rave_linear", LinearArgs), ("rave_maxpool", MaxPoolArgs),

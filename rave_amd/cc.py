@@ -389,14 +389,26 @@ class CachedPQMF(nn.Module):
 def adain(x: torch.Tensor, mean_x: torch.Tensor, std_x: torch.Tensor, mean_y: torch.Tensor, std_y: torch.Tensor,
           num_update_x: torch.Tensor, num_update_y: torch.Tensor, mode: int) -> torch.Tensor:
     """AdaptiveInstanceNormalization.forward, eval mode (rave/blocks.py:899-919):
-    mode 0 transfer, 1 learn_x, 2 learn_y; updates the buffers in place."""
+    mode 0 transfer, 1 learn_x, 2 learn_y; updates the buffers in place.
+
+    Differentiable in ``x`` in every mode (one rave_adain_backward launch): where
+    the call transferred, the cotangent is scaled by std_y / (std_x + 1e-5),
+    elsewhere it passes through.  The statistics are buffers and count as
+    constants, also in the learning modes (mode 1 transfers with the statistics it
+    has just updated; no gradient flows through that update).  The backward reads
+    the counters on the device; no double backward."""
     return torch.ops.rave_amd.adain(x, mean_x, std_x, mean_y, std_y, num_update_x, num_update_y, mode)
 
 
 def noise_synth(amp: torch.Tensor, u: torch.Tensor, n_band: int, noise_bands: int) -> torch.Tensor:
     """NoiseGeneratorV2's filter stage (rave/blocks.py:281-291): pre-sigmoid
     amplitudes (B, n_band noise_bands, F) and U[0,1) draws (B, F, n_band,
-    target) -> filtered noise (B, n_band, F target)."""
+    target) -> filtered noise (B, n_band, F target).
+
+    Differentiable in ``amp`` (one rave_noise_synth_backward launch, bit
+    reproducible).  The draw ``u`` is a constant, as the reference's
+    torch.rand_like is: a ``u`` that requires grad raises NotImplementedError.
+    No double backward."""
     return torch.ops.rave_amd.noise_synth(amp, u, n_band, noise_bands)
 
 

@@ -85,6 +85,26 @@ __global__ __launch_bounds__(kAdaThreads) void adain_kernel(rave_adain_args a) {
     }
 }
 
+// The gradient with respect to x.  The statistics are constants, so a row that
+// was transferred scales its cotangent by std_y / (std_x + 1e-5) in the
+// forward's operation order, and any other row hands it through.  Whether the
+// forward transferred is decided here, from the counters as the forward left
+// them: the host never reads them.  Nothing is written but gx.
+__global__ __launch_bounds__(kAdaThreads) void adain_backward_kernel(rave_adain_backward_args a) {
+    const int c = blockIdx.x, b = blockIdx.y;
+    const float* gy = a.gy + (int64_t)b * a.gy_sb + (int64_t)c * a.gy_sc;
+    float* gx = a.gx + (int64_t)b * a.gx_sb + (int64_t)c * a.gx_sc;
+    const int64_t plane = (int64_t)a.max_batch * a.channels;
+    const int64_t row = (int64_t)(a.row0 + b) * a.channels + c;
+    const bool transfer = a.mode != 2 && a.counters[0] != 0.f && a.counters[1] != 0.f;
+    if (transfer) {
+        const float sx = a.stats[plane + row] + 1e-5f, sy = a.stats[3 * plane + row];
+        for (int t = threadIdx.x; t < a.t_len; t += kAdaThreads) gx[t] = gy[t] / sx * sy;
+    } else if (gx != gy) {
+        for (int t = threadIdx.x; t < a.t_len; t += kAdaThreads) gx[t] = gy[t];
+    }
+}
+
 }  // namespace rave
 
 using namespace rave;
@@ -99,4 +119,16 @@ extern "C" int rave_adain(const rave_adain_args* p, void* stream) {
                    "adain: batch exceeds the statistics buffers (cc.MAX_BATCH_SIZE rows)");
     launch(adain_kernel, dim3(a.channels, a.batch), dim3(kAdaThreads), 0, as_stream(stream), a);
     return launch_status("adain_kernel");
+}
+
+extern "C" int rave_adain_backward(const rave_adain_backward_args* p, void* stream) {
+    RAVE_CHECK_ARG(p && p->gy && p->gx && p->stats && p->counters, "adain_backward: null pointer");
+    const rave_adain_backward_args& a = *p;
+    RAVE_CHECK_ARG(a.batch > 0 && a.channels > 0 && a.t_len > 0, "adain_backward: empty shape");
+    RAVE_CHECK_ARG(a.mode >= 0 && a.mode <= 2,
+                   "adain_backward: mode must be 0 (transfer), 1 (learn_x) or 2 (learn_y)");
+    RAVE_CHECK_ARG(a.row0 >= 0 && a.row0 + a.batch <= a.max_batch,
+                   "adain_backward: batch exceeds the statistics buffers (cc.MAX_BATCH_SIZE rows)");
+    launch(adain_backward_kernel, dim3(a.channels, a.batch), dim3(kAdaThreads), 0, as_stream(stream), a);
+    return launch_status("adain_backward_kernel");
 }

@@ -44,7 +44,8 @@ extern "C" int rave_struct_sizes(int64_t* out, int n) {
         (int64_t)sizeof(rave_stft_args),         (int64_t)sizeof(rave_distance_args),
         (int64_t)sizeof(rave_yin_args),          (int64_t)sizeof(rave_f0_onehot_args),
         (int64_t)sizeof(rave_pqmf_synthesis_backward_args), (int64_t)sizeof(rave_pqmf_analysis_backward_args),
-        (int64_t)sizeof(rave_conv1d_backward_args), (int64_t)sizeof(rave_stft_loss_args),
+        (int64_t)sizeof(rave_conv1d_backward_args), (int64_t)sizeof(rave_noise_backward_args),
+        (int64_t)sizeof(rave_adain_backward_args), (int64_t)sizeof(rave_stft_loss_args),
     };
     const int cnt = (int)(sizeof(sizes) / sizeof(sizes[0]));
     if (!out) return cnt;

@@ -873,8 +873,11 @@ at::Tensor conv_transpose1d_w_autograd(at::Tensor x, at::Tensor weight, at::Tens
 // (mean_x / std_x / mean_y / std_y (max_batch, C, 1), num_update_x / _y (1,)):
 // mode 0 transfer (when both counters are set), 1 learn_x then transfer,
 // 2 learn_y; a learning mode writes the updated statistics back.
-at::Tensor adain_op(at::Tensor x, at::Tensor mean_x, at::Tensor std_x, at::Tensor mean_y, at::Tensor std_y,
-                    at::Tensor num_update_x, at::Tensor num_update_y, int64_t mode) {
+// `kept` (autograd's forward) receives the call's own (4, max_batch, C) statistics
+// and (2,) counters as the kernel left them: post-update copies nobody else holds.
+at::Tensor adain_impl(at::Tensor x, at::Tensor mean_x, at::Tensor std_x, at::Tensor mean_y, at::Tensor std_y,
+                      at::Tensor num_update_x, at::Tensor num_update_y, int64_t mode,
+                      std::pair<at::Tensor, at::Tensor>* kept) {
     seam_tensor(x, "x");
     TORCH_CHECK_VALUE(x.dim() == 3, "x must be (B, C, T)");
     TORCH_CHECK_VALUE(mode >= 0 && mode <= 2, "mode must be 0 (transfer), 1 (learn_x) or 2 (learn_y)");
@@ -909,7 +912,42 @@ at::Tensor adain_op(at::Tensor x, at::Tensor mean_x, at::Tensor std_x, at::Tenso
         std_y.copy_(stats[3].reshape(std_y.sizes()));
         num_update_y.copy_(cnt.narrow(0, 1, 1).reshape(num_update_y.sizes()));
     }
+    if (kept) *kept = {stats, cnt};
     return y;
+}
+
+at::Tensor adain_op(at::Tensor x, at::Tensor mean_x, at::Tensor std_x, at::Tensor mean_y, at::Tensor std_y,
+                    at::Tensor num_update_x, at::Tensor num_update_y, int64_t mode) {
+    return adain_impl(x, mean_x, std_x, mean_y, std_y, num_update_x, num_update_y, mode, nullptr);
+}
+
+// rave_amd::adain_backward -- the gradient of adain with respect to x on
+// rave_adain_backward: gy (B, C, T), stats (4, max_batch, C) and counters (2,)
+// as they stood after the forward call -> gx like gy.  The kernel reads the
+// counters on the device; nothing here waits for them.
+at::Tensor adain_backward_op(at::Tensor gy, at::Tensor stats, at::Tensor counters, int64_t mode) {
+    seam_tensor(gy, "gy");
+    TORCH_CHECK_VALUE(gy.dim() == 3, "gy must be (B, C, T)");
+    TORCH_CHECK_VALUE(mode >= 0 && mode <= 2, "mode must be 0 (transfer), 1 (learn_x) or 2 (learn_y)");
+    c10::hip::HIPGuard g((c10::DeviceIndex)gy.get_device());
+    const int64_t B = gy.size(0), C = gy.size(1), T = gy.size(2);
+    TORCH_CHECK_VALUE(stats.dim() == 3 && stats.size(0) == 4 && stats.size(2) == C,
+                      "stats must be (4, max_batch, C)");
+    TORCH_CHECK_VALUE(counters.numel() == 2, "counters must hold num_update_x and num_update_y");
+    const int64_t mb = stats.size(1);
+    TORCH_CHECK_VALUE(B <= mb, "batch exceeds the AdaIN buffers' max_batch");
+    at::Tensor st = stats.to(gy.device(), at::kFloat).contiguous();
+    at::Tensor cnt = counters.to(gy.device(), at::kFloat).reshape({2}).contiguous();
+    at::Tensor gc = gy.contiguous();
+    at::Tensor gx = at::empty_like(gc);
+    rave_adain_backward_args a{};
+    a.batch = (int)B; a.channels = (int)C; a.t_len = (int)T; a.mode = (int)mode; a.max_batch = (int)mb; a.row0 = 0;
+    a.gy = gc.data_ptr<float>(); a.gy_sb = gc.stride(0); a.gy_sc = gc.stride(1);
+    a.gx = gx.data_ptr<float>(); a.gx_sb = gx.stride(0); a.gx_sc = gx.stride(1);
+    a.stats = st.data_ptr<float>();
+    a.counters = cnt.data_ptr<float>();
+    check(rave_adain_backward(&a, cur_stream(gy)), "adain_backward");
+    return gx;
 }
 
 // rave_amd::noise_synth -- NoiseGeneratorV2's filter stage after its conv stack
@@ -935,6 +973,104 @@ at::Tensor noise_synth_op(at::Tensor amp, at::Tensor u, int64_t n_band, int64_t 
     a.y = y.data_ptr<float>(); a.y_sb = y.stride(0); a.y_sc = y.stride(1);
     check(rave_noise_synth(&a, cur_stream(amp)), "noise_synth");
     return y;
+}
+
+// rave_amd::noise_synth_backward -- the gradient of noise_synth with respect to
+// amp on rave_noise_synth_backward: gy (B, n_band, F * target) and the forward
+// call's amp / u -> gamp like amp.  u is a constant (the reference's rand_like).
+at::Tensor noise_synth_backward_op(at::Tensor gy, at::Tensor amp, at::Tensor u, int64_t n_band, int64_t noise_bands) {
+    seam_tensor(gy, "gy");
+    seam_tensor(amp, "amp");
+    TORCH_CHECK_VALUE(u.is_cuda() && u.scalar_type() == at::kFloat, "u must be a float32 GPU tensor");
+    c10::hip::HIPGuard g((c10::DeviceIndex)amp.get_device());
+    TORCH_CHECK_VALUE(amp.dim() == 3 && amp.size(1) == n_band * noise_bands, "amp must be (B, n_band * noise_bands, F)");
+    const int64_t B = amp.size(0), F = amp.size(2);
+    TORCH_CHECK_VALUE(u.dim() == 4 && u.size(0) == B && u.size(1) == F && u.size(2) == n_band,
+                      "u must be (B, F, n_band, target)");
+    const int64_t target = u.size(3);
+    TORCH_CHECK_VALUE(gy.dim() == 3 && gy.size(0) == B && gy.size(1) == n_band && gy.size(2) == F * target,
+                      "gy must be (B, n_band, F * target)");
+    at::Tensor ac = amp.contiguous(), uc = u.contiguous(), gc = gy.contiguous();
+    at::Tensor gamp = at::empty({B, n_band * noise_bands, F}, amp.options());
+    rave_noise_backward_args a{};
+    a.batch = (int)B; a.frames = (int)F; a.n_band = (int)n_band; a.noise_bands = (int)noise_bands;
+    a.target = (int)target;
+    a.amp = ac.data_ptr<float>(); a.a_sb = ac.stride(0); a.a_sc = ac.stride(1);
+    a.u = uc.data_ptr<float>(); a.u_sb = uc.stride(0);
+    a.gy = gc.data_ptr<float>(); a.gy_sb = gc.stride(0); a.gy_sc = gc.stride(1);
+    a.gamp = gamp.data_ptr<float>(); a.ga_sb = gamp.stride(0); a.ga_sc = gamp.stride(1);
+    check(rave_noise_synth_backward(&a, cur_stream(amp)), "noise_synth_backward");
+    return gamp;
+}
+
+// Autograd for noise_synth and adain, in the manner of the PQMF ops: the forward is
+// the op itself, the backward one kernel call; no double backward.  noise_synth
+// keeps amp and u (u is a constant: asking for its gradient is refused); adain keeps
+// the post-update statistics and counters its call built, never x -- the buffers and
+// the statistics are constants in every mode.
+struct NoiseSynthFn : torch::autograd::Function<NoiseSynthFn> {
+    static at::Tensor forward(torch::autograd::AutogradContext* ctx, at::Tensor amp, at::Tensor u, int64_t n_band,
+                              int64_t noise_bands) {
+        at::AutoDispatchBelowADInplaceOrView below;
+        ctx->save_for_backward({amp, u});
+        ctx->saved_data["n_band"] = n_band;
+        ctx->saved_data["noise_bands"] = noise_bands;
+        return noise_synth_op(amp, u, n_band, noise_bands);
+    }
+    static torch::autograd::variable_list backward(torch::autograd::AutogradContext* ctx,
+                                                   torch::autograd::variable_list grads) {
+        no_double_backward("noise_synth");
+        at::AutoDispatchBelowADInplaceOrView below;
+        const auto saved = ctx->get_saved_variables();
+        at::Tensor gamp = noise_synth_backward_op(grads[0].contiguous(), saved[0], saved[1],
+                                                  ctx->saved_data["n_band"].toInt(),
+                                                  ctx->saved_data["noise_bands"].toInt());
+        return {gamp, at::Tensor(), at::Tensor(), at::Tensor()};
+    }
+};
+
+struct AdainFn : torch::autograd::Function<AdainFn> {
+    static at::Tensor forward(torch::autograd::AutogradContext* ctx, at::Tensor x, at::Tensor mean_x, at::Tensor std_x,
+                              at::Tensor mean_y, at::Tensor std_y, at::Tensor num_update_x, at::Tensor num_update_y,
+                              int64_t mode) {
+        at::AutoDispatchBelowADInplaceOrView below;
+        std::pair<at::Tensor, at::Tensor> kept;
+        at::Tensor y = adain_impl(x, mean_x, std_x, mean_y, std_y, num_update_x, num_update_y, mode, &kept);
+        ctx->save_for_backward({kept.first, kept.second});
+        ctx->saved_data["mode"] = mode;
+        return y;
+    }
+    static torch::autograd::variable_list backward(torch::autograd::AutogradContext* ctx,
+                                                   torch::autograd::variable_list grads) {
+        no_double_backward("adain");
+        at::AutoDispatchBelowADInplaceOrView below;
+        const auto saved = ctx->get_saved_variables();
+        at::Tensor gx = adain_backward_op(grads[0].contiguous(), saved[0], saved[1], ctx->saved_data["mode"].toInt());
+        torch::autograd::variable_list out(8);
+        out[0] = gx;
+        return out;
+    }
+};
+
+at::Tensor noise_synth_autograd(at::Tensor amp, at::Tensor u, int64_t n_band, int64_t noise_bands) {
+    if (at::GradMode::is_enabled() && (amp.requires_grad() || u.requires_grad())) {
+        TORCH_CHECK_NOT_IMPLEMENTED(!u.requires_grad(),
+                                    "noise_synth: the draw u is a constant; its gradient is not implemented");
+        seam_tensor(amp, "amp");
+        return NoiseSynthFn::apply(amp, u, n_band, noise_bands);
+    }
+    at::AutoDispatchBelowADInplaceOrView below;
+    return noise_synth_op(amp, u, n_band, noise_bands);
+}
+
+at::Tensor adain_autograd(at::Tensor x, at::Tensor mean_x, at::Tensor std_x, at::Tensor mean_y, at::Tensor std_y,
+                          at::Tensor num_update_x, at::Tensor num_update_y, int64_t mode) {
+    if (at::GradMode::is_enabled() && x.requires_grad()) {
+        seam_tensor(x, "x");
+        return AdainFn::apply(x, mean_x, std_x, mean_y, std_y, num_update_x, num_update_y, mode);
+    }
+    at::AutoDispatchBelowADInplaceOrView below;
+    return adain_op(x, mean_x, std_x, mean_y, std_y, num_update_x, num_update_y, mode);
 }
 
 // rave_amd::delay_line -- cached_conv's CachedPadding1d on rave_copy: returns
@@ -1047,7 +1183,10 @@ TORCH_LIBRARY(rave_amd, lib) {
     lib.def("adain(Tensor x, Tensor(a!) mean_x, Tensor(b!) std_x, Tensor(c!) mean_y, Tensor(d!) std_y, "
             "Tensor(e!) num_update_x, Tensor(f!) num_update_y, int mode) -> Tensor",
             &adain_op);
+    lib.def("adain_backward(Tensor gy, Tensor stats, Tensor counters, int mode) -> Tensor", &adain_backward_op);
     lib.def("noise_synth(Tensor amp, Tensor u, int n_band, int noise_bands) -> Tensor", &noise_synth_op);
+    lib.def("noise_synth_backward(Tensor gy, Tensor amp, Tensor u, int n_band, int noise_bands) -> Tensor",
+            &noise_synth_backward_op);
     lib.def("delay_line(Tensor x, Tensor(a!) state, bool crop) -> Tensor", &delay_line_op);
     lib.def("rvq_encode(Tensor z, Tensor codebooks) -> Tensor", &rvq_encode_op);
     lib.def("rvq_decode(Tensor idx, Tensor codebooks) -> Tensor", &rvq_decode_op);
@@ -1091,4 +1230,6 @@ TORCH_LIBRARY_IMPL(rave_amd, AutogradCUDA, m) {
     m.impl("pqmf_synthesis", &pqmf_synthesis_autograd);
     m.impl("conv1d_w", &conv1d_w_autograd);
     m.impl("conv_transpose1d_w", &conv_transpose1d_w_autograd);
+    m.impl("adain", &adain_autograd);
+    m.impl("noise_synth", &noise_synth_autograd);
 }

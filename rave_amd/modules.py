@@ -147,7 +147,10 @@ class DilatedUnit(nn.Module):
 class AdaptiveInstanceNormalization(nn.Module):
     """rave/blocks.py:856-919, eval mode, on the rave_adain kernel: the
     reference's buffers (per-row statistics of MAX_BATCH_SIZE rows, learn
-    flags, update counters), transfer / learn_x / learn_y."""
+    flags, update counters), transfer / learn_x / learn_y.  Differentiable in
+    its input in every mode: the identity in training mode, as in the
+    reference, and in eval mode the transfer's derivative with the statistics
+    as constants (``cc.adain``)."""
 
     def __init__(self, dim: int):
         super().__init__()
@@ -236,7 +239,9 @@ class NoiseGeneratorV2(nn.Module):
     """rave/blocks.py:244-291: strided convs (k 2r, padding (r, 0), activation
     between them) -> pre-sigmoid band amplitudes -> the filter stage
     (mod_sigmoid, amp_to_impulse_response, fft_convolve against U[0,1) noise:
-    rave/core.py:66-129) on the rave_noise_synth kernel."""
+    rave/core.py:66-129) on the rave_noise_synth kernel.  Differentiable: the
+    filter stage hands the gradient to the band amplitudes and so to the convs
+    (``cc.noise_synth``); the draw is a constant."""
 
     def __init__(self, in_size: int, hidden_size: int, data_size: int, ratios, noise_bands: int,
                  activation: str = "leaky"):
