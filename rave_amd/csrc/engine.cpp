@@ -321,6 +321,8 @@ void Plan::run(void* const* slots, int n_slots, hipStream_t st) {
 }
 
 // =================================================================== model
+struct Edge;   // one fused path edge (below, "path edges")
+
 struct Model {
     rave_model_config cfg{};
     Graph g;
@@ -330,7 +332,8 @@ struct Model {
     // weight arena (floats)
     std::vector<float> host;
     float* arena = nullptr;
-    std::map<std::pair<std::string, int>, int64_t> w_pack, w_pack_stream, unit_pack;
+    using PackMap = std::map<std::pair<std::string, int>, int64_t>;   // (node name, arithmetic) -> image offset
+    PackMap w_pack, w_pack_stream, unit_pack;
     std::map<std::string, int64_t> bias_off, alpha_off;
     std::set<std::string> unit_ok;     // k=3 names of units with a fused pack in some arithmetic
     int64_t hkf_off = 0, hki_off = 0, spk_off = 0, cb_off = -1;
@@ -412,8 +415,11 @@ struct Model {
     // planning
     std::pair<int, int> conv_launch(const Node& n, const rave_conv1d_args& scalars, bool stream_form, bool timed,
                                     bool allow_ring = true);
+    rave_conv1d_args conv_geom(const Node& n, int B, const View& src, const View& dst, const View* res) const;
     rave_conv1d_args conv_desc(const Node& n, int B, int t_in, const View& src, const View& dst, const View* res,
                                int& t_out) const;
+    PlanOp& emit_conv(Plan& p, const Node& n, const rave_conv1d_args& a, const PackMap& pack, const View& x,
+                      const View& y, const View* res);
     void conv_op(Plan& p, const Node& n, int B, int t_in, const View& src, const View& dst, const View* res);
     double unit_time(const Node& k3, const Node& k1, int B, int T);
     int unit_pick(const Node& k3, int B, int T, bool timed);
@@ -440,16 +446,20 @@ struct Model {
     void synthesis_op(Plan& p, int B, int F, const View& x, const View& y, const View* noise, int pad, int frame0,
                       int x_len);
     void fill_speaker(Plan& p, int B, int Fz, const View& z);
-    // PQMF + edge-conv fusions (csrc/edge_split.hip), split-f16 only
-    rave_edge_args head_desc(int B, int F) const;
-    bool use_head(int B, int T);
+    // PQMF + edge-conv fusions (csrc/edge_split.hip): one path over an Edge description
+    Edge head_edge(int T) const;
+    Edge tail_edge(int F) const;
+    rave_edge_args edge_desc(const Edge& e, int B) const;
+    std::vector<int> edge_cands() const;
+    template <typename Place, typename Pqmf>
+    int edge_pick(const Edge& e, int B, int64_t n_scratch, Place&& place, Pqmf&& pqmf);
+    template <typename Place, typename Pqmf>
+    bool edge_ok(const Edge& e, int ep, int B, int64_t n_scratch, Place& place, Pqmf& pqmf);
+    PlanOp& emit_edge(Plan& p, const Edge& e, int kind, const rave_edge_args& a, const std::string& label,
+                      const View& x, const View& y);
     int head_pick(int B, int T);
-    bool head_ok(int ep, int B, int T);
     void head_op(Plan& p, int B, int T, const View& x, const View& y, const View* fill_z);
-    rave_edge_args tail_desc(int B, int F) const;
-    bool use_tail(int B, int F);
     int tail_pick(int B, int F);
-    bool tail_ok(int ep, int B, int F);
     void tail_op(Plan& p, int B, int F, const View& x, const View& y, const View* noise);
     void rvq_encode_op(Plan& p, int B, int Fz, const View& lat, const View& idx);
     void rvq_decode_op(Plan& p, int B, int Fz, const View& idx, const View& z);
@@ -504,30 +514,35 @@ double Model::time_native(F&& fn, int reps) {
 }
 
 // ------------------------------------------------------------------ conv
-rave_conv1d_args Model::conv_desc(const Node& n, int B, int t_in, const View& src, const View& dst, const View* res,
-                                  int& t_out) const {
+// what a node's one-shot and cached (stream) conv ops have in common; lengths,
+// paddings and out_shift are the caller's
+rave_conv1d_args Model::conv_geom(const Node& n, int B, const View& src, const View& dst, const View* res) const {
     rave_conv1d_args a{};
-    t_out = n.out_len(t_in);
     a.c_in = n.c_in;
     a.c_out = n.c_out;
     a.kernel = n.kernel;
     a.stride = n.stride;
     a.dilation = n.dilation;
+    a.transposed = n.transposed;
     a.act = n.act;
     a.leaky_slope = cfg.leaky_slope;
     a.batch = B;
-    a.t_in = t_in;
-    a.t_out = t_out;
     a.x_sb = src.sb;
     a.x_sc = src.sc;
     a.y_sb = dst.sb;
     a.y_sc = dst.sc;
     a.r_sb = res ? res->sb : 0;
     a.r_sc = res ? res->sc : 0;
+    return a;
+}
+
+rave_conv1d_args Model::conv_desc(const Node& n, int B, int t_in, const View& src, const View& dst, const View* res,
+                                  int& t_out) const {
+    rave_conv1d_args a = conv_geom(n, B, src, dst, res);
+    t_out = n.out_len(t_in);
+    a.t_in = t_in;
+    a.t_out = t_out;
     if (n.transposed) {
-        a.pad_left = 0;
-        a.pad_right = 0;
-        a.transposed = 1;
         a.out_shift = n.stride / 2;
     } else {
         a.pad_left = n.pad_l;
@@ -536,17 +551,19 @@ rave_conv1d_args Model::conv_desc(const Node& n, int B, int t_in, const View& sr
     return a;
 }
 
-template <typename Parts>
-static std::string key_join(const Parts& parts) {
+// A tuning key: the parts joined by '|', numbers in std::to_string's decimal form
+static std::string key_part(const std::string& s) { return s; }
+template <typename T, typename = std::enable_if_t<std::is_arithmetic<T>::value>>
+static std::string key_part(T v) { return std::to_string(v); }
+template <typename... Parts>
+static std::string key_of(const Parts&... parts) {
     std::string k;
-    for (auto& p : parts) {
+    for (const std::string& p : {key_part(parts)...}) {
         if (!k.empty()) k += '|';
         k += p;
     }
     return k;
 }
-static std::string key_of(std::initializer_list<std::string> parts) { return key_join(parts); }
-static std::string key_of(const std::vector<std::string>& parts) { return key_join(parts); }
 
 // (precision, launch config) of one conv op; with autotune every arithmetic and
 // every configuration rave_conv1d_configs lists is timed on scratch tensors of
@@ -559,10 +576,7 @@ std::pair<int, int> Model::conv_launch(const Node& n, const rave_conv1d_args& s,
     // (a choice made without the ring / bf16x3 kernels has a key of its own, so a
     // one-shot plan's ring choice is never replayed on unaligned stream rows and a
     // stream plan's restricted choice never limits a one-shot plan)
-    std::vector<std::string> kp = {"conv", n.name, std::to_string(stream_form), std::to_string(s.batch),
-                                   std::to_string(s.t_in)};
-    if (!allow_ring) kp.push_back("noring");
-    const std::string key = key_of(kp);
+    const std::string key = key_of("conv", n.name, stream_form, s.batch, s.t_in) + (allow_ring ? "" : "|noring");
     if (!tuned.count(key) && (precs.size() > 1 || timed || autotune)) {
         const int B = s.batch;
         const int64_t nx = (int64_t)B * n.c_in * s.t_in, ny = (int64_t)B * n.c_out * s.t_out;
@@ -640,34 +654,43 @@ std::pair<int, int> Model::conv_launch(const Node& n, const rave_conv1d_args& s,
     return {precs[0], 0};
 }
 
+// One conv op into a plan, one-shot or cached: `a` is complete but for its
+// pointers (geometry, precision, config), `pack` the weight images of its form
+PlanOp& Model::emit_conv(Plan& p, const Node& n, const rave_conv1d_args& a, const PackMap& pack, const View& x,
+                         const View& y, const View* res) {
+    const int64_t w_off = pack.at({n.name, a.precision});
+    // split-K slab the launcher wants (shapes only)
+    rave_conv1d_args q = a;
+    q.x = q.alpha = (const float*)arena;
+    q.y = (float*)arena;
+    q.residual = res ? (const float*)arena : nullptr;
+    q.weight = aptr(w_off);
+    const int64_t nsk = rave_conv1d_workspace(&q);
+    if (nsk < 0) fail(RAVE_ERR_ARG, "conv " + n.name + ": workspace query failed: " + rave_last_error());
+    PlanOp& o = p.add(RAVE_OP_CONV, a, n.name);
+    View wv = arena_view(w_off);
+    View bv = n.bias ? arena_view(bias_off.at(n.name)) : View{};
+    View av = n.act == RAVE_ACT_SNAKE ? arena_view(alpha_off.at(n.alpha)) : View{};
+    View sk = p.splitk(nsk);
+    rave_conv1d_args& A = *reinterpret_cast<rave_conv1d_args*>(o.op.u.raw);
+    p.bind(o, A, A.x, &x);
+    p.bind(o, A, A.y, &y);
+    p.bind(o, A, A.residual, res);
+    p.bind(o, A, A.weight, &wv);
+    p.bind(o, A, A.bias, n.bias ? &bv : nullptr);
+    p.bind(o, A, A.alpha, n.act == RAVE_ACT_SNAKE ? &av : nullptr);
+    p.bind(o, A, A.partial, nsk > 0 ? &sk : nullptr);
+    o.prec = a.precision;
+    return o;
+}
+
 void Model::conv_op(Plan& p, const Node& n, int B, int t_in, const View& src, const View& dst, const View* res) {
     int t_out;
     rave_conv1d_args a = conv_desc(n, B, t_in, src, dst, res, t_out);
     const auto pc = conv_launch(n, a, false, false);
     a.precision = pc.first;
     a.config = pc.second;
-    // split-K slab the launcher wants (shapes only)
-    rave_conv1d_args q = a;
-    q.x = q.weight = q.alpha = (const float*)arena;
-    q.y = (float*)arena;
-    q.residual = res ? (const float*)arena : nullptr;
-    q.weight = aptr(w_pack.at({n.name, pc.first}));
-    const int64_t nsk = rave_conv1d_workspace(&q);
-    if (nsk < 0) fail(RAVE_ERR_ARG, "conv " + n.name + ": workspace query failed: " + rave_last_error());
-    PlanOp& o = p.add(RAVE_OP_CONV, a, n.name);
-    View wv = arena_view(w_pack.at({n.name, pc.first}));
-    View bv = n.bias ? arena_view(bias_off.at(n.name)) : View{};
-    View av = n.act == RAVE_ACT_SNAKE ? arena_view(alpha_off.at(n.alpha)) : View{};
-    View sk = p.splitk(nsk);
-    rave_conv1d_args& A = *reinterpret_cast<rave_conv1d_args*>(o.op.u.raw);
-    p.bind(o, A, A.x, &src);
-    p.bind(o, A, A.y, &dst);
-    p.bind(o, A, A.residual, res);
-    p.bind(o, A, A.weight, &wv);
-    p.bind(o, A, A.bias, n.bias ? &bv : nullptr);
-    p.bind(o, A, A.alpha, n.act == RAVE_ACT_SNAKE ? &av : nullptr);
-    p.bind(o, A, A.partial, nsk > 0 ? &sk : nullptr);
-    o.prec = pc.first;
+    PlanOp& o = emit_conv(p, n, a, w_pack, src, dst, res);
     const double taps = n.transposed ? 2.0 : (double)n.kernel;
     o.flops = 2.0 * B * n.c_out * t_out * n.c_in * taps;
     o.bytes = 4.0 * ((double)B * n.c_in * t_in + (double)B * n.c_out * t_out * (res ? 2 : 1) +
@@ -707,7 +730,7 @@ rave_unit_args Model::unit_desc(const Node& k3, const Node& k1, int B, int T, in
 
 double Model::unit_time(const Node& k3, const Node& k1, int B, int T) {
     unit_pick(k3, B, T, true);
-    return tuned.at(key_of({"unit", k3.name, std::to_string(B), std::to_string(T)})).second;
+    return tuned.at(key_of("unit", k3.name, B, T)).second;
 }
 
 // the faster arithmetic of the fused unit kernel for this shape (timed when
@@ -725,7 +748,7 @@ int Model::unit_pick(const Node& k3, int B, int T, bool timed) {
         q.precision = cands[0];
         if (rave_unit_workspace(&q) <= 0) return cands[0];   // one form: nothing to time
     }
-    const std::string key = key_of({"unit", k3.name, std::to_string(B), std::to_string(T)});
+    const std::string key = key_of("unit", k3.name, B, T);
     if (!tuned.count(key)) {
         const Node* k1 = nullptr;
         for (const Node* n : g.convs())
@@ -770,7 +793,7 @@ int Model::unit_pick(const Node& k3, int B, int T, bool timed) {
 
 // the cooperative form the tuning chose: 0 none, 1 groups of C / 128, 2 the wide group
 int Model::unit_coop(const Node& k3, int B, int T) {
-    const std::string key = key_of({"unit", k3.name, std::to_string(B), std::to_string(T)});
+    const std::string key = key_of("unit", k3.name, B, T);
     auto it = tuned.find(key);
     return it != tuned.end() ? ((int)it->second.first >> 8) : 0;
 }
@@ -779,7 +802,7 @@ int Model::unit_coop(const Node& k3, int B, int T) {
 // with several arithmetics the faster by measurement.
 bool Model::fuse_unit(const Node& k3, const Node& k1, int B, int T) {
     if (precs.size() == 1) return true;
-    const std::string key = key_of({"fuse", k3.name, std::to_string(B), std::to_string(T)});
+    const std::string key = key_of("fuse", k3.name, B, T);
     if (!tuned.count(key)) {
         const double fused = unit_time(k3, k1, B, T);
         View src = ws_view(0, (int64_t)k3.c_in * T, T), tmp = ws_view(0, (int64_t)k3.c_out * T, T);
@@ -788,9 +811,8 @@ bool Model::fuse_unit(const Node& k3, const Node& k1, int B, int T) {
         conv_launch(k3, s3, false, true);
         rave_conv1d_args s1 = conv_desc(k1, B, T, tmp, tmp, &src, t1);
         conv_launch(k1, s1, false, true);
-        const double split =
-            tuned.at(key_of({"conv", k3.name, "0", std::to_string(B), std::to_string(T)})).second +
-            tuned.at(key_of({"conv", k1.name, "0", std::to_string(B), std::to_string(T)})).second;
+        const double split = tuned.at(key_of("conv", k3.name, 0, B, T)).second +
+                             tuned.at(key_of("conv", k1.name, 0, B, T)).second;
         tuned[key] = {fused <= split ? 1 : 0, std::min(fused, split)};
     }
     return tuned.at(key).first != 0;
@@ -799,7 +821,7 @@ bool Model::fuse_unit(const Node& k3, const Node& k1, int B, int T) {
 double Model::unit_best_ms(const Node& k3, const Node& k1, int B, int T) {
     if (precs.size() > 1) {
         fuse_unit(k3, k1, B, T);
-        return tuned.at(key_of({"fuse", k3.name, std::to_string(B), std::to_string(T)})).second;
+        return tuned.at(key_of("fuse", k3.name, B, T)).second;
     }
     return unit_time(k3, k1, B, T);
 }
@@ -952,7 +974,7 @@ rave_stack_args Model::stack_desc(const std::vector<std::pair<const Node*, const
 bool Model::use_stack(const std::vector<std::pair<const Node*, const Node*>>& run, int B, int T) {
     if (stack_prec() < 0) return false;
     if (precs.size() == 1 && !autotune) return true;
-    const std::string key = key_of({"stack", run[0].first->name, std::to_string(B), std::to_string(T)});
+    const std::string key = key_of("stack", run[0].first->name, B, T);
     if (!tuned.count(key)) {
         rave_stack_args s = stack_desc(run, B, T);
         const int64_t n_el = (int64_t)B * s.channels * T;
@@ -1165,11 +1187,10 @@ void Model::analysis_op(Plan& p, int B, int T, const View& x, const View& y, int
         q.x = sc;
         q.y = sc + nx + 64;
         q.hkf = arena + hkf_off;
-        a.precision = pqmf_prec(key_of({"pqa", std::to_string(B), std::to_string(T), std::to_string(t_in)}),
-                                [&](int pr, hipStream_t st) {
-                                    q.precision = pr;
-                                    return rave_pqmf_analysis(&q, st);
-                                });
+        a.precision = pqmf_prec(key_of("pqa", B, T, t_in), [&](int pr, hipStream_t st) {
+            q.precision = pr;
+            return rave_pqmf_analysis(&q, st);
+        });
     }
     PlanOp& o = p.add(RAVE_OP_PQMF_ANALYSIS, a, "pqmf_analysis");
     o.prec = a.precision;
@@ -1208,12 +1229,10 @@ void Model::synthesis_op(Plan& p, int B, int F, const View& x, const View& y, co
         q.y = sc + ((nx + 63) / 64 + 1) * 64;     // 16-byte aligned
         q.noise = nullptr;
         q.hki = arena + hki_off;
-        a.precision = pqmf_prec(key_of({"pqs", std::to_string(B), std::to_string(F), std::to_string(x_len),
-                                        std::to_string(pad)}),
-                                [&](int pr, hipStream_t st) {
-                                    q.precision = pr;
-                                    return rave_pqmf_synthesis(&q, st);
-                                });
+        a.precision = pqmf_prec(key_of("pqs", B, F, x_len, pad), [&](int pr, hipStream_t st) {
+            q.precision = pr;
+            return rave_pqmf_synthesis(&q, st);
+        });
     }
     PlanOp& o = p.add(RAVE_OP_PQMF_SYNTHESIS, a, "pqmf_synthesis");
     o.prec = a.precision;
@@ -1287,35 +1306,58 @@ void Model::fill_speaker(Plan& p, int B, int Fz, const View& z) {
 // (GeneratorV2's last conv + epilogue -> synthesis).  Used where split-f16 is
 // one of the model's arithmetics, the shapes are the kernels', and (with
 // autotuning) the fused launch beats the two separate ops at their best.
-rave_edge_args Model::head_desc(int B, int F) const {
-    const Node& n = g.encoder.front();
-    rave_edge_args a{};
-    a.batch = B;
-    a.frames = F;
-    a.conv_c_in = n.c_in;
-    a.conv_c_out = n.c_out;
-    a.conv_kernel = n.kernel;
-    a.conv_pad_left = n.pad_l;
-    a.pqmf_taps = taps_a;
-    a.pqmf_pad_left = get_padding(taps_a, 1, cfg.causal).first;
-    a.act = n.act;
-    a.leaky_slope = cfg.leaky_slope;
-    return a;
+// What the two share is written once over this description; the scratch layout
+// of the timing launches, the PQMF op, and each op's own strides and extra
+// binds stay with head_pick / head_op and tail_pick / tail_op.
+struct Edge {
+    const Node& n;               // the conv next to the PQMF
+    const char* word;            // of the tuning key word|arithmetic|B|len
+    int len, F;                  // the key's length (head: samples T, tail: frames F); frames
+    int taps;                    // of the PQMF filter
+    int64_t filt16, filt32;      // filter images: split-f16, exact fp32 (-1: shape unsupported)
+    int w_bf3;                   // arithmetic of the conv weight image the bf16x3 form reads
+    int mode;                    // rave_edge_args.mode (0 in the head)
+    int (*launch)(const rave_edge_args*, void*);
+    bool shape_ok;               // the kernel's shape gate
+    int64_t filt(int ep) const { return ep == RAVE_PREC_SPLIT16 ? filt16 : filt32; }
+    int wprec(int ep) const { return ep == RAVE_PREC_BF16X3 ? w_bf3 : ep; }
+};
+
+// what both kernels ask of the conv
+static bool edge_conv_ok(const rave_model_config& c, const Node& n) {
+    return c.n_band == 16 && n.kernel == 7 && n.stride == 1 && n.dilation == 1 && !n.transposed && n.adain.empty();
 }
 
-rave_edge_args Model::tail_desc(int B, int F) const {
+// the bf16x3 head runs the analysis in bf16x3 and the conv in exact fp32: the ring image
+Edge Model::head_edge(int T) const {
+    const Node& n = g.encoder.front();
+    const int F = T / cfg.n_band;
+    const bool ok = edge_conv_ok(cfg, n) && n.act == RAVE_ACT_NONE && n.c_in <= 8 && n.c_out <= 64 &&
+                    F * cfg.n_band == T;
+    return {n, "head", T, F, taps_a, head_filt_off, head_filt32_off, RAVE_PREC_F32_RING, 0, rave_encoder_head, ok};
+}
+
+Edge Model::tail_edge(int F) const {
     const Node& n = g.decoder.back();
+    const int c_want = cfg.amplitude_modulation ? 2 * cfg.n_band : cfg.n_band;
+    const bool ok = edge_conv_ok(cfg, n) && n.c_in == 64 && n.c_out == c_want &&
+                    (n.act == RAVE_ACT_LEAKY || n.act == RAVE_ACT_SNAKE);
+    return {n, "tail", F, F, taps_s, tail_filt_off, tail_filt32_off, RAVE_PREC_BF16X3,
+            cfg.amplitude_modulation ? 1 : 2, rave_decoder_tail, ok};
+}
+
+rave_edge_args Model::edge_desc(const Edge& e, int B) const {
     rave_edge_args a{};
     a.batch = B;
-    a.frames = F;
-    a.conv_c_in = n.c_in;
-    a.conv_c_out = n.c_out;
-    a.conv_kernel = n.kernel;
-    a.conv_pad_left = n.pad_l;
-    a.pqmf_taps = taps_s;
-    a.pqmf_pad_left = get_padding(taps_s, 1, cfg.causal).first;
-    a.mode = cfg.amplitude_modulation ? 1 : 2;
-    a.act = n.act;
+    a.frames = e.F;
+    a.conv_c_in = e.n.c_in;
+    a.conv_c_out = e.n.c_out;
+    a.conv_kernel = e.n.kernel;
+    a.conv_pad_left = e.n.pad_l;
+    a.pqmf_taps = e.taps;
+    a.pqmf_pad_left = get_padding(e.taps, 1, cfg.causal).first;
+    a.mode = e.mode;
+    a.act = e.n.act;
     a.leaky_slope = cfg.leaky_slope;
     return a;
 }
@@ -1326,18 +1368,24 @@ static bool edges_enabled() {
     return !(e && e[0] == '0');
 }
 
-// the fused head's arithmetic for (B, T), or -1 for the two separate ops: the
-// model's edge arithmetic, and in f32_bf3 models also the bf16x3 analysis form
-// (exact-fp32 conv), whichever is timed faster
-int Model::head_pick(int B, int T) {
+// the model's edge arithmetic, and in f32_bf3 models also the bf16x3 form (the
+// head's analysis / the tail's conv in bf16x3, the other half exact fp32)
+std::vector<int> Model::edge_cands() const {
     std::vector<int> cands = {edge_prec()};
     if (edge_prec() == RAVE_PREC_F32_RING && std::find(precs.begin(), precs.end(), (int)RAVE_PREC_BF16X3) != precs.end())
         cands.push_back(RAVE_PREC_BF16X3);
+    return cands;
+}
+
+// the fused edge's arithmetic for (B, e.len), or -1 for the two separate ops:
+// of the candidates edge_ok passes, the one timed faster
+template <typename Place, typename Pqmf>
+int Model::edge_pick(const Edge& e, int B, int64_t n_scratch, Place&& place, Pqmf&& pqmf) {
     int best = -1;
     double bms = 1e30;
-    for (int ep : cands) {
-        if (!head_ok(ep, B, T)) continue;
-        const double ms = tuned.at(key_of({"head", std::to_string(ep), std::to_string(B), std::to_string(T)})).second;
+    for (int ep : edge_cands()) {
+        if (!edge_ok(e, ep, B, n_scratch, place, pqmf)) continue;
+        const double ms = tuned.at(key_of(e.word, ep, B, e.len)).second;
         if (best < 0 || ms < bms) {
             best = ep;
             bms = ms;
@@ -1346,41 +1394,83 @@ int Model::head_pick(int B, int T) {
     return best;
 }
 
-bool Model::use_head(int B, int T) { return head_pick(B, T) >= 0; }
-
-// the head's conv weight image: the ring image for the exact-fp32 and bf16x3 forms
-static int head_wprec(int ep) { return ep == RAVE_PREC_BF16X3 ? RAVE_PREC_F32_RING : ep; }
-
-bool Model::head_ok(int ep, int B, int T) {
-    const int64_t filt = ep == RAVE_PREC_SPLIT16 ? head_filt_off : head_filt32_off;
-    if (!edges_enabled() || ep < 0 || filt < 0) return false;
-    const Node& n = g.encoder.front();
-    const int F = T / cfg.n_band;
-    if (!w_pack.count({n.name, head_wprec(ep)})) return false;
-    if (cfg.n_band != 16 || n.kernel != 7 || n.stride != 1 || n.dilation != 1 || n.act != RAVE_ACT_NONE ||
-        n.transposed || n.c_in > 8 || n.c_out > 64 || !n.adain.empty() || F * cfg.n_band != T)
-        return false;
-    const std::string key = key_of({"head", std::to_string(ep), std::to_string(B), std::to_string(T)});
+// Whether the edge runs fused in arithmetic `ep` at this shape: the gates, then
+// (once per key) the fused launch timed against the two ops at their best, on
+// `n_scratch` floats of scratch.  `place(a, sc)` points the fused launch's
+// operands, and the caller's PQMF op's, into the scratch; `pqmf(precision,
+// stream)` launches that op.
+template <typename Place, typename Pqmf>
+bool Model::edge_ok(const Edge& e, int ep, int B, int64_t n_scratch, Place& place, Pqmf& pqmf) {
+    const Node& n = e.n;
+    if (!edges_enabled() || ep < 0 || e.filt(ep) < 0) return false;
+    if (!w_pack.count({n.name, e.wprec(ep)}) || !e.shape_ok) return false;
+    const std::string key = key_of(e.word, ep, B, e.len);
     if (!tuned.count(key)) {
-        rave_edge_args a = head_desc(B, F);
-        const int64_t nx = (int64_t)B * T, ny = (int64_t)B * n.c_out * F, nb = (int64_t)B * n.c_in * F;
-        float* sc = scratch_buf(nx + ny + nb + 256);
-        a.x = sc;
-        a.x_sb = T;
-        a.y = sc + nx + 64;
-        a.y_sb = (int64_t)n.c_out * F;
-        a.y_sc = F;
-        a.weight = aptr(w_pack.at({n.name, head_wprec(ep)}));
+        rave_edge_args a = edge_desc(e, B);
+        place(a, scratch_buf(n_scratch));
+        a.weight = aptr(w_pack.at({n.name, e.wprec(ep)}));
         a.bias = n.bias ? aptr(bias_off.at(n.name)) : nullptr;
-        a.filter = aptr(filt);
+        a.alpha = n.act == RAVE_ACT_SNAKE ? aptr(alpha_off.at(n.alpha)) : nullptr;
+        a.filter = aptr(e.filt(ep));
         a.precision = ep;
-        const double fused = time_native([&](hipStream_t st) { return rave_encoder_head(&a, st); });
+        const double fused = time_native([&](hipStream_t st) { return e.launch(&a, st); });
         double split = 1e30;
         if (precs.size() == 1) {
             split = fused >= 0 ? 1e30 : -1.0;
         } else {
-            // the two ops at their best: analysis in either arithmetic, the conv's tuned launch
-            rave_pqmf_analysis_args q{};
+            // the two ops at their best: the PQMF op in either arithmetic, the conv's tuned launch
+            double tq = 1e30;
+            for (int pr : {RAVE_PREC_F32, RAVE_PREC_SPLIT16}) {
+                if (pr == RAVE_PREC_SPLIT16 && ep != RAVE_PREC_SPLIT16) continue;   // the exact model's own ops
+                const double ms = time_native([&](hipStream_t st) { return pqmf(pr, st); });
+                if (ms >= 0) tq = std::min(tq, ms);
+            }
+            View dummy;
+            int t_out;
+            const rave_conv1d_args cd = conv_desc(n, B, e.F, dummy, dummy, nullptr, t_out);
+            (void)conv_launch(n, cd, false, true);
+            const auto it = tuned.find(key_of("conv", n.name, 0, B, e.F));
+            split = tq + (it != tuned.end() ? it->second.second : 1e30);
+        }
+        tuned[key] = {fused >= 0 && fused < split ? 1 : 0, fused};
+    }
+    return tuned.at(key).first == 1;
+}
+
+// The fused op into a plan: `a` complete but for its pointers; x, y and what
+// both edges read from the arena are bound here, the rest by the caller
+PlanOp& Model::emit_edge(Plan& p, const Edge& e, int kind, const rave_edge_args& a, const std::string& label,
+                         const View& x, const View& y) {
+    const Node& n = e.n;
+    PlanOp& o = p.add(kind, a, label);
+    rave_edge_args& A = *reinterpret_cast<rave_edge_args*>(o.op.u.raw);
+    View wv = arena_view(w_pack.at({n.name, e.wprec(a.precision)}));
+    View bv = n.bias ? arena_view(bias_off.at(n.name)) : View{};
+    View hv = arena_view(e.filt(a.precision));
+    p.bind(o, A, A.x, &x);
+    p.bind(o, A, A.y, &y);
+    p.bind(o, A, A.weight, &wv);
+    p.bind(o, A, A.bias, n.bias ? &bv : nullptr);
+    p.bind(o, A, A.filter, &hv);
+    o.prec = a.precision;
+    return o;
+}
+
+// the head's timing launches: x | y | the bands tensor of the two-op path
+int Model::head_pick(int B, int T) {
+    const Edge e = head_edge(T);
+    const Node& n = e.n;
+    const int F = e.F;
+    const int64_t nx = (int64_t)B * T, ny = (int64_t)B * n.c_out * F, nb = (int64_t)B * n.c_in * F;
+    rave_pqmf_analysis_args q{};
+    return edge_pick(
+        e, B, nx + ny + nb + 256,
+        [&](rave_edge_args& a, float* sc) {
+            a.x = sc;
+            a.x_sb = T;
+            a.y = sc + nx + 64;
+            a.y_sb = (int64_t)n.c_out * F;
+            a.y_sc = F;
             q.n_band = cfg.n_band;
             q.taps = taps_a;
             q.n_out_bands = n.c_in;
@@ -1394,29 +1484,18 @@ bool Model::head_ok(int ep, int B, int T) {
             q.y_sb = (int64_t)n.c_in * F;
             q.y_sc = F;
             q.hkf = aptr(hkf_off);
-            double ta = 1e30;
-            for (int pr : {RAVE_PREC_F32, RAVE_PREC_SPLIT16}) {
-                if (pr == RAVE_PREC_SPLIT16 && ep != RAVE_PREC_SPLIT16) continue;   // the exact model's own ops
-                q.precision = pr;
-                const double ms = time_native([&](hipStream_t st) { return rave_pqmf_analysis(&q, st); });
-                if (ms >= 0) ta = std::min(ta, ms);
-            }
-            View dummy;
-            int t_out;
-            const rave_conv1d_args cd = conv_desc(n, B, F, dummy, dummy, nullptr, t_out);
-            (void)conv_launch(n, cd, false, true);
-            const auto it = tuned.find(key_of({"conv", n.name, "0", std::to_string(B), std::to_string(F)}));
-            split = ta + (it != tuned.end() ? it->second.second : 1e30);
-        }
-        tuned[key] = {fused >= 0 && fused < split ? 1 : 0, fused};
-    }
-    return tuned.at(key).first == 1;
+        },
+        [&](int pr, hipStream_t st) {
+            q.precision = pr;
+            return rave_pqmf_analysis(&q, st);
+        });
 }
 
 void Model::head_op(Plan& p, int B, int T, const View& x, const View& y, const View* fill_z) {
-    const Node& n = g.encoder.front();
-    const int F = T / cfg.n_band;
-    rave_edge_args a = head_desc(B, F);
+    const Edge e = head_edge(T);
+    const Node& n = e.n;
+    const int F = e.F;
+    rave_edge_args a = edge_desc(e, B);
     a.x_sb = x.sb;
     a.y_sb = y.sb;
     a.y_sc = y.sc;
@@ -1429,76 +1508,29 @@ void Model::head_op(Plan& p, int B, int T, const View& x, const View& y, const V
     const int ep = head_pick(B, T);
     if (ep < 0) fail(RAVE_ERR_STATE, "encoder head: no fused form for this shape");
     a.precision = ep;
-    PlanOp& o = p.add(RAVE_OP_HEAD, a, "encoder_head:pqmf_analysis+" + n.name);
+    PlanOp& o = emit_edge(p, e, RAVE_OP_HEAD, a, "encoder_head:pqmf_analysis+" + n.name, x, y);
     rave_edge_args& A = *reinterpret_cast<rave_edge_args*>(o.op.u.raw);
-    View wv = arena_view(w_pack.at({n.name, head_wprec(ep)}));
-    View bv = n.bias ? arena_view(bias_off.at(n.name)) : View{};
-    View hv = arena_view(ep == RAVE_PREC_SPLIT16 ? head_filt_off : head_filt32_off);
     View sv = arena_view(spk_off);
-    p.bind(o, A, A.x, &x);
-    p.bind(o, A, A.y, &y);
-    p.bind(o, A, A.weight, &wv);
-    p.bind(o, A, A.bias, n.bias ? &bv : nullptr);
-    p.bind(o, A, A.filter, &hv);
     p.bind(o, A, A.fill_y, a.fill_channels ? fill_z : nullptr);
     p.bind(o, A, A.fill_values, a.fill_channels ? &sv : nullptr);
-    o.prec = ep;
     o.flops = 2.0 * B * F * ((double)n.c_in * taps_a + (double)n.c_out * n.c_in * n.kernel);
     o.bytes = 4.0 * ((double)B * T + (double)B * n.c_out * F);
 }
 
-// the fused tail's arithmetic for (B, F), or -1 for the two separate ops: the
-// model's edge arithmetic, and in f32_bf3 models also the bf16x3 conv form
-// (exact-fp32 synthesis), whichever is timed faster
+// the tail's timing launches: x | the two-op path's conv output | y
 int Model::tail_pick(int B, int F) {
-    std::vector<int> cands = {edge_prec()};
-    if (edge_prec() == RAVE_PREC_F32_RING && std::find(precs.begin(), precs.end(), (int)RAVE_PREC_BF16X3) != precs.end())
-        cands.push_back(RAVE_PREC_BF16X3);
-    int best = -1;
-    double bms = 1e30;
-    for (int ep : cands) {
-        if (!tail_ok(ep, B, F)) continue;
-        const double ms = tuned.at(key_of({"tail", std::to_string(ep), std::to_string(B), std::to_string(F)})).second;
-        if (best < 0 || ms < bms) {
-            best = ep;
-            bms = ms;
-        }
-    }
-    return best;
-}
-
-bool Model::use_tail(int B, int F) { return tail_pick(B, F) >= 0; }
-
-bool Model::tail_ok(int ep, int B, int F) {
-    const int64_t filt = ep == RAVE_PREC_SPLIT16 ? tail_filt_off : tail_filt32_off;
-    if (!edges_enabled() || ep < 0 || filt < 0) return false;
-    const Node& n = g.decoder.back();
-    if (!w_pack.count({n.name, ep})) return false;
-    const int c_want = cfg.amplitude_modulation ? 2 * cfg.n_band : cfg.n_band;
-    if (cfg.n_band != 16 || n.kernel != 7 || n.stride != 1 || n.dilation != 1 || n.transposed || n.c_in != 64 ||
-        n.c_out != c_want || (n.act != RAVE_ACT_LEAKY && n.act != RAVE_ACT_SNAKE) || !n.adain.empty())
-        return false;
-    const std::string key = key_of({"tail", std::to_string(ep), std::to_string(B), std::to_string(F)});
-    if (!tuned.count(key)) {
-        rave_edge_args a = tail_desc(B, F);
-        const int64_t nx = (int64_t)B * n.c_in * F, nw = (int64_t)B * n.c_out * F, ny = (int64_t)B * F * cfg.n_band;
-        float* sc = scratch_buf(nx + nw + ny + 256);
-        a.x = sc;
-        a.x_sb = (int64_t)n.c_in * F;
-        a.x_sc = F;
-        a.y = sc + ((nx + nw + 63) / 64 + 1) * 64;     // 16-byte aligned
-        a.y_sb = (int64_t)F * cfg.n_band;
-        a.weight = aptr(w_pack.at({n.name, ep}));
-        a.bias = n.bias ? aptr(bias_off.at(n.name)) : nullptr;
-        a.alpha = n.act == RAVE_ACT_SNAKE ? aptr(alpha_off.at(n.alpha)) : nullptr;
-        a.filter = aptr(filt);
-        a.precision = ep;
-        const double fused = time_native([&](hipStream_t st) { return rave_decoder_tail(&a, st); });
-        double split = 1e30;
-        if (precs.size() == 1) {
-            split = fused >= 0 ? 1e30 : -1.0;
-        } else {
-            rave_pqmf_synthesis_args q{};
+    const Edge e = tail_edge(F);
+    const Node& n = e.n;
+    const int64_t nx = (int64_t)B * n.c_in * F, nw = (int64_t)B * n.c_out * F, ny = (int64_t)B * F * cfg.n_band;
+    rave_pqmf_synthesis_args q{};
+    return edge_pick(
+        e, B, nx + nw + ny + 256,
+        [&](rave_edge_args& a, float* sc) {
+            a.x = sc;
+            a.x_sb = (int64_t)n.c_in * F;
+            a.x_sc = F;
+            a.y = sc + ((nx + nw + 63) / 64 + 1) * 64;     // 16-byte aligned
+            a.y_sb = (int64_t)F * cfg.n_band;
             q.n_band = cfg.n_band;
             q.taps = taps_s;
             q.batch = B;
@@ -1511,28 +1543,17 @@ bool Model::tail_ok(int ep, int B, int F) {
             q.y = a.y;
             q.y_sb = a.y_sb;
             q.hki = aptr(hki_off);
-            double ts = 1e30;
-            for (int pr : {RAVE_PREC_F32, RAVE_PREC_SPLIT16}) {
-                if (pr == RAVE_PREC_SPLIT16 && ep != RAVE_PREC_SPLIT16) continue;   // the exact model's own ops
-                q.precision = pr;
-                const double ms = time_native([&](hipStream_t st) { return rave_pqmf_synthesis(&q, st); });
-                if (ms >= 0) ts = std::min(ts, ms);
-            }
-            View dummy;
-            int t_out;
-            const rave_conv1d_args cd = conv_desc(n, B, F, dummy, dummy, nullptr, t_out);
-            (void)conv_launch(n, cd, false, true);
-            const auto it = tuned.find(key_of({"conv", n.name, "0", std::to_string(B), std::to_string(F)}));
-            split = ts + (it != tuned.end() ? it->second.second : 1e30);
-        }
-        tuned[key] = {fused >= 0 && fused < split ? 1 : 0, fused};
-    }
-    return tuned.at(key).first == 1;
+        },
+        [&](int pr, hipStream_t st) {
+            q.precision = pr;
+            return rave_pqmf_synthesis(&q, st);
+        });
 }
 
 void Model::tail_op(Plan& p, int B, int F, const View& x, const View& y, const View* noise) {
-    const Node& n = g.decoder.back();
-    rave_edge_args a = tail_desc(B, F);
+    const Edge e = tail_edge(F);
+    const Node& n = e.n;
+    rave_edge_args a = edge_desc(e, B);
     a.x_sb = x.sb;
     a.x_sc = x.sc;
     a.y_sb = y.sb;
@@ -1541,20 +1562,11 @@ void Model::tail_op(Plan& p, int B, int F, const View& x, const View& y, const V
     const int ep = tail_pick(B, F);
     if (ep < 0) fail(RAVE_ERR_STATE, "decoder tail: no fused form for this shape");
     a.precision = ep;
-    PlanOp& o = p.add(RAVE_OP_TAIL, a, "decoder_tail:" + n.name + "+pqmf_synthesis");
+    PlanOp& o = emit_edge(p, e, RAVE_OP_TAIL, a, "decoder_tail:" + n.name + "+pqmf_synthesis", x, y);
     rave_edge_args& A = *reinterpret_cast<rave_edge_args*>(o.op.u.raw);
-    View wv = arena_view(w_pack.at({n.name, ep}));
-    View bv = n.bias ? arena_view(bias_off.at(n.name)) : View{};
     View av = n.act == RAVE_ACT_SNAKE ? arena_view(alpha_off.at(n.alpha)) : View{};
-    View hv = arena_view(ep == RAVE_PREC_SPLIT16 ? tail_filt_off : tail_filt32_off);
-    p.bind(o, A, A.x, &x);
-    p.bind(o, A, A.y, &y);
-    p.bind(o, A, A.weight, &wv);
-    p.bind(o, A, A.bias, n.bias ? &bv : nullptr);
     p.bind(o, A, A.alpha, n.act == RAVE_ACT_SNAKE ? &av : nullptr);
-    p.bind(o, A, A.filter, &hv);
     p.bind(o, A, A.noise, noise);
-    o.prec = ep;
     o.flops = 2.0 * B * F * ((double)n.c_out * n.c_in * n.kernel + (double)cfg.n_band * cfg.n_band * taps_s);
     o.bytes = 4.0 * ((double)B * n.c_in * F + (double)B * F * cfg.n_band + (noise ? (double)B * cfg.n_band * F : 0.0));
 }
@@ -1629,7 +1641,7 @@ Plan& Model::encode_plan(int B, int T, bool codes) {
     else lat = io_view(1, (int64_t)(cfg.latent_size + cfg.speaker_size) * Fz, Fz);
     const View spk_z = lat.at((int64_t)cfg.latent_size * Fz);
     std::vector<const Node*> nodes = ptrs_of(g.encoder);
-    if (use_head(B, T)) {
+    if (head_pick(B, T) >= 0) {
         // analysis + the first conv (+ the speaker fill) in one launch
         const Node& n0 = *nodes.front();
         // workspace laid out as the two-op path lays it (the bands tensor's slot,
@@ -1669,7 +1681,7 @@ Plan& Model::decode_plan(int B, int Fz, bool codes) {
         z = io_view(0, (int64_t)dec_in * Fz, Fz);
     }
     const int F = Fz * hop / cfg.n_band;
-    const bool tail = use_tail(B, F);
+    const bool tail = tail_pick(B, F) >= 0;
     const Node& wnode = g.decoder.back();
     std::map<std::string, View> outputs;
     View wave, feat;
@@ -2434,26 +2446,11 @@ static void conv_stream(Model* m, Plan& p, const Node& n, int B, std::map<std::s
         const StreamBuf& rb = bufs.at(n.residual);
         res = rb.v.at(rb.h - n.res_delay);    // AlignBranches: the identity branch, delayed
     }
-    rave_conv1d_args a{};
-    a.c_in = n.c_in;
-    a.c_out = n.c_out;
-    a.kernel = n.kernel;
-    a.stride = n.stride;
-    a.dilation = n.dilation;
+    // the cached form: no right padding, no out_shift, lengths from the buffers
+    rave_conv1d_args a = m->conv_geom(n, B, x, y, has_res ? &res : nullptr);
     a.pad_left = n.transposed ? 1 : 0;
-    a.transposed = n.transposed;
-    a.out_shift = 0;
-    a.act = n.act;
-    a.leaky_slope = m->cfg.leaky_slope;
-    a.batch = B;
     a.t_in = need - sd + src.t;       // [cache l+r | block delayed by sd]
     a.t_out = dst.t;
-    a.x_sb = x.sb;
-    a.x_sc = x.sc;
-    a.y_sb = y.sb;
-    a.y_sc = y.sc;
-    a.r_sb = has_res ? res.sb : 0;
-    a.r_sc = has_res ? res.sc : 0;
     // the fp32 ring kernels read 16-byte row pieces: workspace rows whose stride
     // and start (the history offset) are multiples of 4 floats, t_in % 4 == 0
     const bool vec_rows = x.p.kind == PRef::WS && x.sc % 4 == 0 && x.sb % 4 == 0 && x.p.off % 16 == 0 &&
@@ -2461,28 +2458,8 @@ static void conv_stream(Model* m, Plan& p, const Node& n, int B, std::map<std::s
     const auto pc = m->conv_launch(n, a, n.transposed, false, vec_rows);
     a.precision = pc.first;
     a.config = pc.second;
-    auto& pack = n.transposed ? m->w_pack_stream : m->w_pack;   // ConvTranspose: the cached (out_shift 0) form
-    rave_conv1d_args q = a;
-    q.x = q.alpha = (const float*)m->arena;
-    q.y = (float*)m->arena;
-    q.residual = has_res ? (const float*)m->arena : nullptr;
-    q.weight = m->aptr(pack.at({n.name, pc.first}));
-    const int64_t nsk = rave_conv1d_workspace(&q);
-    if (nsk < 0) fail(RAVE_ERR_ARG, "conv " + n.name + ": workspace query failed: " + rave_last_error());
-    PlanOp& o = p.add(RAVE_OP_CONV, a, n.name);
-    rave_conv1d_args& A = *reinterpret_cast<rave_conv1d_args*>(o.op.u.raw);
-    View wv = m->arena_view(pack.at({n.name, pc.first}));
-    View bv = n.bias ? m->arena_view(m->bias_off.at(n.name)) : View{};
-    View av = n.act == RAVE_ACT_SNAKE ? m->arena_view(m->alpha_off.at(n.alpha)) : View{};
-    View sk = p.splitk(nsk);
-    p.bind(o, A, A.x, &x);
-    p.bind(o, A, A.y, &y);
-    p.bind(o, A, A.residual, has_res ? &res : nullptr);
-    p.bind(o, A, A.weight, &wv);
-    p.bind(o, A, A.bias, n.bias ? &bv : nullptr);
-    p.bind(o, A, A.alpha, n.act == RAVE_ACT_SNAKE ? &av : nullptr);
-    p.bind(o, A, A.partial, nsk > 0 ? &sk : nullptr);
-    o.prec = pc.first;
+    // ConvTranspose: the cached (out_shift 0) weight image
+    m->emit_conv(p, n, a, n.transposed ? m->w_pack_stream : m->w_pack, x, y, has_res ? &res : nullptr);
 }
 
 // The cached conv sequence of one stream plan.  A Residual(DilatedUnit) whose
