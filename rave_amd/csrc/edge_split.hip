@@ -786,8 +786,10 @@ __global__ __launch_bounds__(kEdgeNT) void decoder_tail_kernel(rave_edge_args a,
             const int f = f0 + w;
             const bool ok = f >= 0 && f < F;
             if (nzc && ok) out = out + nzc[f];
-            // tanh(x) = 1 - 2 / (e^2x + 1): saturates to +-1 through inf / 0
-            out = 1.0f - 2.0f * __builtin_amdgcn_rcpf(__expf(2.0f * out) + 1.0f);
+            // tanhf as the separate synthesis (pqmf.hip), not 1 - 2 / (e^2x + 1): that form
+            // rounds e^2x beside 1, an absolute error near 2^-23 whatever the result's size,
+            // which is many ulps of a small tanh and shows in outputs that few taps reach
+            out = tanhf(out);
             if ((c_out & 1) && !(f & 1)) out = -out;
             if (w < kTSW) {
                 if constexpr (BF) {

@@ -62,9 +62,10 @@ def _finish(acc, S, bias, res, dtype, cond):
     return (acc, S) if cond else acc
 
 
-def conv(x, w, bias, alpha, res, k, s, d, pl, t_out, act, slope, dtype=np.float64, cond=False):
+def conv(x, w, bias, alpha, res, k, s, d, pl, t_out, act, slope, dtype=np.float64, cond=False, chunk=None):
     """rave_conv1d, transposed = 0.  x (B, c_in, t_in), w (c_out, c_in, k) -> (B, c_out, t_out);
-    with ``cond`` also S."""
+    with ``cond`` also S.  ``chunk``: input channels per K-chunk where the kernel's is not
+    CHUNK[k] (the fused edges' convs, tests/edge_ref.py)."""
     x = np.asarray(x)
     B, c_in, _ = x.shape
     wd = np.asarray(w, dtype).astype(np.float64)
@@ -74,9 +75,10 @@ def conv(x, w, bias, alpha, res, k, s, d, pl, t_out, act, slope, dtype=np.float6
     at = s * np.arange(t_out)
     acc = np.zeros((B, c_out, t_out), dtype)
     S = np.zeros((B, c_out, t_out), np.float64)
-    for c0 in range(0, c_in, CHUNK[k]):
+    chunk = chunk or CHUNK[k]
+    for c0 in range(0, c_in, chunk):
         for j in range(k):
-            for ci in range(c0, min(c0 + CHUNK[k], c_in)):
+            for ci in range(c0, min(c0 + chunk, c_in)):
                 wv, av = wd[None, :, ci, j, None], ap[:, ci][:, None, at + j * d]
                 acc = _fma(wv, av, acc)
                 if cond:

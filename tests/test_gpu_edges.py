@@ -11,7 +11,8 @@ Tolerances: layer outputs 2e-5 relative to max|ref| (as the single-layer tests);
 model outputs 1e-4 max-abs (north star).  Ragged lengths (frames not a
 multiple of the 256-frame tiles) and both padding modes are covered, in both
 arithmetics: split-f16 and exact fp32 (precision RAVE_PREC_F32_RING: the
-ring weight image and the fp32 filter image)."""
+ring weight image and the fp32 filter image).
+The tile, halo and option edges, against e_ref: tests/test_gpu_edge_sweep.py."""
 import ctypes as C
 
 import numpy as np
