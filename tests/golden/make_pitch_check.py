@@ -13,7 +13,8 @@ from FCPE, so its quantiser is checked by handing the module a stand-in
 
 For every case of tests/pitch_ref.py, in float64 and float32: the sliced cmdf
 (1e-12 / 1e-5 relative to its largest value; float32 differs only by the
-thread-dependent order of the FFT), the period index and f0; for the table of
+thread-dependent order of the FFT), the period index and f0; the same in
+float64 for every case of the edge sweep (SWEEP); for the table of
 tests/pitch_ref.py and each case's contour: the one-hot and the normalised
 log-f0.  Writes nothing; runs on the CPU only.
 
@@ -56,6 +57,27 @@ def main():
             print(f"  {case} {str(dtype)[6:]}: cmdf off by {dev:.1e}, f0 {'equal' if same else 'DIFFERS'} "
                   f"({int((f0 > 0).sum())} of {f0.numel()} voiced)")
             assert same or dtype == torch.float32, case
+    # the edge sweep's inputs (tests/pitch_ref.py SWEEP), in float64: frames, cmdf
+    # (NaN where the reference's is: the rows holding a NaN or inf), index and f0
+    worst = 0.0
+    for name, c in R.SWEEP.items():
+        x = torch.tensor(R.sweep_input(name), dtype=torch.float64)
+        fr = P._frame(x, c["L"], c["stride"])
+        assert torch.equal(torch.nan_to_num(fr), torch.nan_to_num(R.frame(x, c["L"], c["stride"]))), name
+        assert fr.shape[-2] == c["frames"], name
+        cmdf = P._diff(fr, c["tau_max"])[..., c["tau_min"]:]
+        mine, idx, f0 = R.analyse(x, c["sr"], c["pmin"], c["pmax"], c["stride_s"], c["threshold"])
+        assert torch.equal(torch.isnan(cmdf), torch.isnan(mine)), name
+        a, b = torch.nan_to_num(cmdf), torch.nan_to_num(mine)
+        dev = float((a - b).abs().max() / b.abs().max().clamp(min=1.0))
+        worst = max(worst, dev)
+        assert dev <= 1e-12, (name, dev)
+        assert torch.equal(P._search(mine, c["tau_max"], c["threshold"]), idx), name
+        ref_f0 = P.estimate(x, c["sr"], c["pmin"], c["pmax"], c["stride_s"], c["threshold"])
+        assert torch.equal(ref_f0, f0), name
+        t = R.sweep_truth(name)
+        assert torch.equal(idx, torch.from_numpy(t["idx_fft64"])) and bool((idx.numpy()[t["poisoned"]] == 0).all()), name
+    print(f"  sweep: {len(R.SWEEP)} cases in float64, cmdf off by at most {worst:.1e}, index and f0 equal")
     # the quantiser, fed the YIN contour in FCPE's place: (B, frames, 1), 0 = unvoiced
     contours = [torch.from_numpy(R.table_f0()).reshape(1, -1)]
     contours += [R.reference(case, "float32")[2].reshape(-1, R.geometry(case)[4]) for case in R.CASES]
